@@ -11,6 +11,13 @@ pattern phase per rank); no collective in the data path -- RCCL only for the bar
 max-over-ranks time and the final counter reduction.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--packets P] [--tbn 10,3,3]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`,
+`ms_per_step`).  --full adds everything else to the line: the check of the timed work against its
+payloads, per-kernel durations and the roofline (with a rocprofv3 child run), the host-inclusive
+rates, BASELINE configs 3 and 4, the relay and multi-stream legs and the CPU baseline.
+--dump-outputs DIR writes what the last timed step returned (dump_outputs).
 """
 from __future__ import annotations
 
@@ -319,6 +326,41 @@ def timed(fn, steps):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps
+
+
+DUMP_ROWS = 8192      # sampled rows of the codeword and payload arrays (whole rows, every byte)
+DUMP_PACKETS = 1 << 20  # per-packet arrays are written whole up to this many packets
+
+
+def dump_outputs(dirname, cw, wl, out, ol, suffix=""):
+    """--dump-outputs: what the last timed step handed its caller -- the encoder's codewords and
+    wire sizes, the decoder's payload rows and lengths -- as DIR/<name>.npy, under 64 MB in all at
+    the default size: the two length arrays whole (float32), a position-weighted byte sum of every
+    codeword and payload row (float64, exact: below 2^31), and DUMP_ROWS whole rows of each array at
+    fixed, seeded row numbers (float32).  Arrays longer than their limit are sampled the same way.
+    The inputs depend on the arguments alone, so two builds can be compared file by file."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+
+    def sample(x, limit, seed):
+        if x.shape[0] <= limit:
+            return x
+        idx = np.sort(np.random.default_rng(seed).choice(x.shape[0], limit, replace=False))
+        return x[torch.from_numpy(idx).to(x.device)]
+
+    def row_sums(x, chunk=65536):
+        w = torch.arange(1, x.shape[1] + 1, device=x.device, dtype=torch.int32)
+        return torch.cat([(x[a:a + chunk].to(torch.int32) * w).sum(1, dtype=torch.int64)
+                          for a in range(0, x.shape[0], chunk)])
+
+    arrays = {"wire_sizes": (sample(wl, DUMP_PACKETS, 1), np.float32),
+              "payload_lengths": (sample(ol, DUMP_PACKETS, 2), np.float32),
+              "codeword_row_sums": (sample(row_sums(cw), DUMP_PACKETS, 1), np.float64),
+              "payload_row_sums": (sample(row_sums(out), DUMP_PACKETS, 2), np.float64),
+              "codewords_sample": (sample(cw, DUMP_ROWS, 3), np.float32),
+              "payloads_sample": (sample(out, DUMP_ROWS, 4), np.float32)}
+    for name, (t, dt) in arrays.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), t.cpu().numpy().astype(dt))
 
 
 def quiet_cpu_group(sample_s=0.2):
@@ -843,6 +885,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--packets", type=int, default=1_000_000, help="decoded packets per GPU")
     ap.add_argument("--tbn", default="10,3,3")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the timed work and measure everything else "
+                         "(per-kernel times and roofline, host-inclusive rates, configs 3 and 4, relay and "
+                         "multi-stream legs, CPU baseline); the --no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--stream-id", type=int, default=None,
                     help="payload seed and pattern phase of this stream (default: the rank); a single-rank "
                          "run with --stream-id r reproduces rank r's stream of a multi-rank run")
@@ -1024,6 +1072,38 @@ def main():
         print(json.dumps({"rocprof_child": True, "ms_per_step": elapsed / args.steps * 1e3}), flush=True)
         if world == 1 and not args.no_extra_configs:
             relay_chain_launches(20)
+        return
+
+    if args.dump_outputs:  # the last timed step's buffers (--pipeline: the codewords it wrote last)
+        last = (pstate["i"] - 1) % len(cws) if args.pipeline else 0
+        dump_outputs(args.dump_outputs, cws[last], wls[last], out, ol, f"_rank{rank}" if rank else "")
+
+    if not args.full:  # the plain run: the headline line alone
+        if rank == 0:
+            print(json.dumps({
+                "metric": "GiB/s device-resident erasure encode+decode, 300B pkts, T=10; %HBM roofline",
+                "value": round(world * P * L / (elapsed / args.steps) / 2**30, 3),
+                "unit": "GiB/s",
+                "n_gpus": world,
+                "steps": args.steps,
+                "warmup": args.warmup,
+                "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+                "higher_is_better": True,
+                "scaling": "weak",
+                "vs_baseline": None,
+                "dtype": "u8",
+                "config": {"workload": f"encode {Pf} + decode {P} x 300B packets per GPU, one stream "
+                                       f"per GPU, (T,B,N)=({T},{B},{N})",
+                           "T": T, "B": B, "N": N, "packets_per_gpu": P},
+                "env": fec_env,
+                "host_submit_ms_per_step": round(t_submit / args.steps * 1e3, 4),
+                "step_launch": ("hipGraph replay" if args.graph else "eager launches") +
+                               ("; batch i's recovery beside batch i+1's encode (--pipeline)" if args.pipeline else ""),
+                "device_warmup": {"seconds": args.warm_seconds, "untimed_steps": warm_steps},
+                "full": False}), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
         return
 
     # correctness of the timed work (outside the timed region): round trip + planner agreement

@@ -73,9 +73,9 @@ void gf_gen_rs_matrix(unsigned char* a, int m, int k);
 }
 """
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "include")) or
-                                shutil.which("g++") is None,
-                                reason="needs the reference checkout and g++ (not on the GPU box)")
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "include")) or
+                                     shutil.which("g++") is None,
+                                     reason="needs the reference checkout and g++ (not on the GPU box)")
 
 
 def _overlay(tmp_path, swap: bool):
@@ -97,12 +97,14 @@ def _syntax(flags, src):
                           [os.path.join(REF, "src", src)], capture_output=True, text=True, timeout=120)
 
 
+@needs_reference
 @pytest.mark.parametrize("src", CALLERS)
 def test_reference_caller_compiles_against_dropin(tmp_path, src):
     r = _syntax(_overlay(tmp_path, swap=True), src)
     assert r.returncode == 0, f"{src} does not compile under the header swap:\n{r.stderr[-3000:]}"
 
 
+@needs_reference
 def test_stubs_alone_compile_the_original_headers(tmp_path):
     """Control: the same stubs with the reference's original headers compile the same callers, so a
     failure above is the drop-in header's, not the stubs'."""
@@ -112,6 +114,7 @@ def test_stubs_alone_compile_the_original_headers(tmp_path):
         assert r.returncode == 0, f"{src}:\n{r.stderr[-2000:]}"
 
 
+@needs_reference
 def test_swapped_reference_links_without_isal(tmp_path):
     """The reference's application layers and simulators (LINKED), compiled under the full swap --
     basicOperations.h and codingOperations.h included, so neither basicOperations.cpp,
@@ -147,8 +150,8 @@ def test_reference_signature_functions_equal_oracle(tmp_path):
     (fec_amd_refops.h, host code over the library's field) against the oracle's restatements of
     basicOperations.cpp / codingOperations.cpp on random matrices and erasure patterns."""
     import fec_erasure_code_unit_test_relay_amd as fec
-    if not os.path.exists(fec.LIB_PATH):
-        pytest.skip("needs the built libfec_amd.so")
+    if not os.path.exists(fec.LIB_PATH) or shutil.which("g++") is None:
+        pytest.skip("needs g++ and the built libfec_amd.so")
     libdir = os.path.dirname(fec.LIB_PATH)
     exe = tmp_path / "refops_test"
     r = subprocess.run(["g++", "-O2", "-x", "c++", "-std=c++17", os.path.join(ROOT, "tests", "cpp", "refops_test.cpp"),

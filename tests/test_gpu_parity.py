@@ -474,7 +474,7 @@ def test_config5_bench_two_ranks_gloo():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["FEC_BENCH_BACKEND"] = "gloo"
     common = ["--steps", "3", "--warmup", "1", "--warm-seconds", "0.2", "--packets", "1000000",
-              "--no-extra-configs", "--no-cpu-baseline", "--no-host-inclusive"]
+              "--full", "--no-extra-configs", "--no-cpu-baseline", "--no-host-inclusive"]
     d = _bench_json(["--gpus", "2"] + common, env)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak"
     assert d["verified"] is True  # every rank's round trip (bench.py reduces the flags over the ranks)
@@ -488,6 +488,38 @@ def test_config5_bench_two_ranks_gloo():
     for sid in (0, 1):
         single = _bench_json(["--gpus", "1", "--stream-id", str(sid)] + common, env)
         assert single["per_rank"] == [ranks[sid]], (single["per_rank"], ranks[sid])
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run times --steps steps and prints the headline line alone; --dump-outputs
+    writes the last step's codewords, wire sizes, payloads and lengths as float .npy files (whole at
+    this size: 5000 packets are fewer than the sampled rows), equal to the library's own encode and
+    decode of the same stream."""
+    from fec_erasure_code_unit_test_relay_amd.streams import stream_pattern, stream_seed
+    T, P = 10, 5000
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    d = _bench_json(["--gpus", "1", "--steps", "2", "--warmup", "1", "--warm-seconds", "0", "--packets", str(P),
+                     "--dump-outputs", str(tmp_path)], env)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "GiB/s" and d["dtype"] == "u8"
+    assert d["higher_is_better"] is True and d["metric"].startswith("GiB/s device-resident erasure encode+decode")
+    assert abs(d["value"] - P * L / (d["ms_per_step"] * 1e-3) / 2**30) <= 1e-2 * d["value"]
+    for moved in ("verified", "roofline", "host_inclusive", "configs", "cpu_baseline", "kernels_ms_per_launch"):
+        assert moved not in d
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(got) == ["codeword_row_sums", "codewords_sample", "payload_lengths", "payload_row_sums",
+                           "payloads_sample", "wire_sizes"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 * 10**6
+    c = fec.Codec(L, T, 3, 3)
+    payload = fec.fill_payload(0, P + T, L, stream_seed(0))
+    cw, wl = c.encode(payload)
+    out, ln = c.decode(cw, torch.from_numpy(stream_pattern(P + T, 0)).cuda())
+    for name, ref in (("codewords_sample", cw), ("wire_sizes", wl), ("payloads_sample", out), ("payload_lengths", ln)):
+        assert got[name].shape == tuple(ref.shape) and (got[name] == ref.cpu().numpy()).all(), name
+    for name, ref in (("codeword_row_sums", cw), ("payload_row_sums", out)):
+        w = np.arange(1, ref.shape[1] + 1, dtype=np.int64)
+        assert (got[name] == (ref.cpu().numpy().astype(np.int64) * w).sum(1)).all(), name
 
 
 def test_cpp_dropin_program(tmp_path):

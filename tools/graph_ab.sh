@@ -7,7 +7,7 @@ TAG=${1:-graph_ab}
 shift
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
-B="--no-cpu-baseline --no-host-inclusive --no-extra-configs $*"
+B="--full --no-cpu-baseline --no-host-inclusive --no-extra-configs $*"
 i=0
 for a in "--graph" "" "--graph" "" "--graph --steps 100" "--steps 100"; do
     i=$((i + 1))

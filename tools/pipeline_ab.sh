@@ -9,7 +9,7 @@ cd $R
 i=0
 for a in "" "--pipeline" "" "--pipeline" "" "--pipeline"; do
     i=$((i + 1))
-    timeout -k 10 200 python -u bench.py --no-extra-configs --no-cpu-baseline --no-host-inclusive $a > $OUT/run$i.json 2> $OUT/run$i.err || { echo "bench failed: $a"; tail -20 $OUT/run$i.err; exit 1; }
+    timeout -k 10 200 python -u bench.py --full --no-extra-configs --no-cpu-baseline --no-host-inclusive $a > $OUT/run$i.json 2> $OUT/run$i.err || { echo "bench failed: $a"; tail -20 $OUT/run$i.err; exit 1; }
     python3 - "$OUT/run$i.json" "$a" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
