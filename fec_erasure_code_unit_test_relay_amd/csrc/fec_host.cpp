@@ -233,6 +233,19 @@ std::shared_ptr<const DecodeRules> shared_decode_rules(int T, int B, int N) {
     return std::shared_ptr<const DecodeRules>(slot, &slot->rules);
 }
 
+void full_window_decode_rows(int k, int n, const uint8_t* er, uint8_t* rows) {
+    std::fill(rows, rows + n * n, uint8_t(0));
+    for (int q = 0; q < n; ++q) rows[q * n + q] = 1;
+    uint32_t mask = 0;
+    for (int c = 0; c < n; ++c) mask |= (er[c] ? 1u : 0u) << c;
+    const int cnt = __builtin_popcount(mask);
+    if (cnt == 0 || cnt >= n - k + 1) return;
+    const auto rules = shared_decode_rules(n - 1, n - k, n - k);
+    const uint8_t* e = rules->entry(n, mask);
+    for (int i = 0; i < k; ++i)
+        if (((mask >> i) & 1u) && e[i] != 0xFF) std::copy(e + k + i * n, e + k + (i + 1) * n, rows + i * n);
+}
+
 // ------------------------------------------------------------------------------------------
 // StreamPlanner
 // ------------------------------------------------------------------------------------------

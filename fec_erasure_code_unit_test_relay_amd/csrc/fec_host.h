@@ -32,6 +32,8 @@ namespace fec {
 constexpr int kMaxK = 16;   // k = T-N+1
 constexpr int kMaxN = 32;   // n = k+B (erasure masks are 32-bit)
 constexpr int kMaxRuleN = 17;  // decode-rule tables are built for n <= 17 (2^17 masks)
+constexpr int kTTot = 10;      // T_TOT (FEC_Macro.h:32)
+constexpr int kEstimationCycle = 1000 / 10;  // ESTIMATION_WINDOW_SIZE / ..._REDUCTION_FACTOR (FEC_Macro.h:54-55)
 
 // ------------------------------------------------------------------------------------------
 // GF(2^8)
@@ -133,6 +135,12 @@ std::shared_ptr<const DecodeRules> shared_decode_rules(int T, int B, int N);
 // The rule for one (w, mask), computed directly (used to build the table and by tests).
 void decode_rule(const uint8_t* G, int k, int n, int w, uint32_t mask, uint8_t* sel,
                  uint8_t* col /* k*w */);
+
+// The symbol-wise decoders' full-window decode (decodeBlock T = n-1, t = 0 on the window's n flags,
+// Decoder_Symbol_Wise.cpp:570-573, :640-643) on unit vectors, as coefficient rows: position q's
+// value after the decode = row q over the n positions.  The identity unless 0 < erasures < n-k+1
+// (an erased slot holds zeros); n <= kMaxRuleN.
+void full_window_decode_rows(int k, int n, const uint8_t* er, uint8_t* rows /* n x n */);
 
 // ------------------------------------------------------------------------------------------
 // StreamPlanner: symbolic decoder.  Output of one step is the fate of packet x = t - T.

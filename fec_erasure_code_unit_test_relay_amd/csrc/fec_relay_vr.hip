@@ -497,7 +497,7 @@ int fec_relay_vr_run(fec_relay_vr* r, const uint8_t* d_payload, const uint8_t* h
         // the streams this run uses: type 2's chains go to kQueues of them, type 3's codes one each (the
         // fork, the join and the drain touch only these: joining idle streams too cost the gather's
         // start ~60 us behind the last chain, profiles/r06/r06zd_*)
-        const bool per_code = r->type == 3 || std::getenv("FEC_RELAY_VR_PER_CODE") != nullptr;  // (A/B for type 2)
+        const bool per_code = r->type == 3;
         const int nst = std::min<int>(per_code ? fec_relay_vr::kStreams : fec_relay_vr::kQueues,
                                       static_cast<int>(r->codes.size()));
         // any return before the join below (an error) drains the side streams first: otherwise the

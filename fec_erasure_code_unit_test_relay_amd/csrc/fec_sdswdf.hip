@@ -56,7 +56,7 @@
 namespace fec {
 namespace {
 
-constexpr int kTT = 10;             // T_TOT (FEC_Macro.h:32)
+constexpr int kTT = kTTot;
 constexpr int kSlots = 3 * kTT;     // codeword_vector_state_dependent rows
 constexpr int kHdr = kTT + 1;       // header entries per row (and frame header bytes)
 constexpr int kSdThreads = 256;
@@ -788,12 +788,8 @@ struct SdTileArgs {
     int F;
 };
 
-#ifndef FEC_SD_PASS
-#define FEC_SD_PASS 1
-#endif
-// packets per lane and tile (halo rows staged once per tile).  2 measured slower: relay 268 vs
-// 246 us, destination 129 vs 121 us per 360 000 packets (profiles/r05/relay/r05zp_*).
-constexpr int kSdPass = FEC_SD_PASS;
+// One packet per lane and tile of 4 * (64 / NS4) packets (two per lane measured slower: relay 268 vs
+// 246 us, destination 129 vs 121 us per 360 000 packets, profiles/r05/relay/r05zp_*).
 constexpr int kSdMaxTile = 64;  // packets per tile the record-id slots hold
 // shift = the row offset of an output row's diagonal: relay row index reads source packet
 // t - (N-1) + (K-1-index) + p; destination row s reads frame t - s - (N2-1-q).
@@ -807,7 +803,7 @@ __global__ __launch_bounds__(256) void fec_sd_tile_kernel(SdTileArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     for (int i = tid; i < 1040; i += 256) gexp[i] = i < 510 ? a.gf[i] : 0;
     for (int i = tid; i < 256; i += 256) glog[i] = i ? a.gf[512 + i] : 512;
-    const int S = a.S, NS4 = (S + 3) >> 2, ppw = 64 / NS4, TP = kSdPass * 4 * ppw;
+    const int S = a.S, NS4 = (S + 3) >> 2, ppw = 64 / NS4, TP = 4 * ppw;
     if (TP > kSdMaxTile) return;  // never launched so (sd_tile_fit): the record ids would overrun their slots
     const int64_t t0 = static_cast<int64_t>(blockIdx.x) * TP;
     const int nt = static_cast<int>(min<int64_t>(TP, a.P - t0));
@@ -834,13 +830,11 @@ __global__ __launch_bounds__(256) void fec_sd_tile_kernel(SdTileArgs a) {
     if (tid < nt) srec[tid] = a.plan[t0 + tid];
     __syncthreads();
     const int pl = lane / NS4, g = lane - pl * NS4;
-    uint32_t A4[kSdPass][ROWS];
-#pragma unroll
-    for (int ps = 0; ps < kSdPass; ++ps) {
-    const int tl = (ps * 4 + wv) * ppw + pl;  // the lane's packet in the tile
+    uint32_t A4[ROWS];
+    const int tl = wv * ppw + pl;  // the lane's packet in the tile
     const bool on = pl < ppw && tl < nt;
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r) A4[ps][r] = 0;
+    for (int r = 0; r < ROWS; ++r) A4[r] = 0;
     if (on) {
         const int rid = srec[tl];
         const uint16_t* eb = a.ent + a.ent_off[rid];
@@ -864,19 +858,14 @@ __global__ __launch_bounds__(256) void fec_sd_tile_kernel(SdTileArgs a) {
                 }
                 acc ^= w;
             }
-            A4[ps][r] = acc;
+            A4[r] = acc;
         }
-    }
     }
     __syncthreads();  // the staged rows are read: the output tile takes their place
     const int OB = RELAY ? a.F : S * K;                 // output row bytes
     const int64_t ob0 = t0 * OB;
     const int odl = static_cast<int>(ob0 & 15);
     uint8_t* ot = raw + odl;                            // output byte b of row tl at ot[tl * OB + b]
-#pragma unroll
-    for (int ps = 0; ps < kSdPass; ++ps) {
-    const int tl = (ps * 4 + wv) * ppw + pl;
-    const bool on = pl < ppw && tl < nt;
     if (on) {
         uint8_t* orow = ot + tl * OB;
 #pragma unroll
@@ -886,7 +875,7 @@ __global__ __launch_bounds__(256) void fec_sd_tile_kernel(SdTileArgs a) {
             const bool keep = j < a.blocks;  // blocks past ceil(max_payload/k)+1 stay zero (:184-185)
             uint8_t* d = orow + (RELAY ? 4 + kHdr + j * ROWS : j * K);
 #pragma unroll
-            for (int r = 0; r < ROWS; ++r) d[r] = keep ? static_cast<uint8_t>(A4[ps][r] >> (8 * q)) : 0;
+            for (int r = 0; r < ROWS; ++r) d[r] = keep ? static_cast<uint8_t>(A4[r] >> (8 * q)) : 0;
         }
         if (RELAY && g == 0) {  // [size BE16][header 11][2 zero bytes] ... [zero tail]
             const int size = (S + 1) * ROWS;
@@ -898,7 +887,6 @@ __global__ __launch_bounds__(256) void fec_sd_tile_kernel(SdTileArgs a) {
             orow[3 + kHdr] = 0;
             for (int o = 4 + kHdr + S * ROWS; o < OB; ++o) orow[o] = 0;
         }
-    }
     }
     __syncthreads();
     const int obytes = nt * OB;
@@ -913,22 +901,22 @@ __global__ __launch_bounds__(256) void fec_sd_tile_kernel(SdTileArgs a) {
     }
 }
 
-#define FEC_SD_TILE_LIST(X) \
+#define FEC_SDT_SHAPES(X) \
     X(11, 11, 11) X(10, 11, 11) X(9, 11, 11) X(8, 11, 11) X(7, 11, 11) X(6, 11, 11) X(5, 11, 11) X(4, 11, 11) \
     X(6, 11, 9) X(8, 11, 9)
-#define FEC_SD_TILE_INST(K, N, N2) \
+#define FEC_SDT_INST(K, N, N2) \
     template __global__ void fec_sd_tile_kernel<K, N, N2, true>(SdTileArgs); \
     template __global__ void fec_sd_tile_kernel<K, N2, K, false>(SdTileArgs);
-FEC_SD_TILE_LIST(FEC_SD_TILE_INST)
+FEC_SDT_SHAPES(FEC_SDT_INST)
 
 // The tile kernel for the relay (k, n1, n2) / the destination (k, n2), or nullptr.
 const void* sd_tile_kernel_for(bool relay, int k, int n1, int n2) {
-#define FEC_SD_TILE_CASE(K, N, N2)                                                                        \
+#define FEC_SDT_CASE(K, N, N2)                                                                        \
     if (k == K && n2 == N2 && (!relay || n1 == N))                                                     \
         return relay ? reinterpret_cast<const void*>(&fec_sd_tile_kernel<K, N, N2, true>)               \
                      : reinterpret_cast<const void*>(&fec_sd_tile_kernel<K, N2, K, false>);
-    FEC_SD_TILE_LIST(FEC_SD_TILE_CASE)
-#undef FEC_SD_TILE_CASE
+    FEC_SDT_SHAPES(FEC_SDT_CASE)
+#undef FEC_SDT_CASE
     return nullptr;
 }
 
@@ -1105,7 +1093,7 @@ namespace fec {
 bool sd_tile_fit(bool relay, int k, int n1, int n2, int S, int F, int64_t stride, int* TP_out, int64_t* lds_out) {
     const int NS4 = (S + 3) / 4;
     if (!sd_tile_kernel_for(relay, k, n1, n2) || NS4 > 64) return false;
-    const int TP = kSdPass * 4 * (64 / NS4);
+    const int TP = 4 * (64 / NS4);
     if (TP > kSdMaxTile) return false;
     const int N = relay ? n1 : n2, ROWS = relay ? n2 : k;
     const int back = relay ? (N - 1) + (ROWS - 1) - (k - 1) : (ROWS - 1) + (N - 1);
@@ -1125,8 +1113,6 @@ namespace {
 // 1 when the tile kernel does not apply (the caller launches the per-(packet, block) kernel).
 int launch_tile(fec_sdswdf* w, bool relay, const fec::RecordTable& tab, const uint8_t* d_in, int64_t stride,
                 int64_t P, uint8_t* d_out, hipStream_t s) {
-    const char* e = std::getenv("FEC_SD_TILE");
-    if (e && e[0] == '0') return 1;
     const int k = w->g1.k, n1 = w->g1.n, n2 = w->g2.n, S = w->g1.S;
     const void* kern = fec::sd_tile_kernel_for(relay, k, n1, n2);
     int TP = 0;
@@ -1271,22 +1257,6 @@ int sw_run(SwCtx& c, SwApplyArgs& a) {
     return FEC_OK;
 }
 
-// The decode rule of a full window (decodeBlock T = n-1, t = 0) on unit vectors, as coefficient rows:
-// position q's value after the decode = row q over the n positions.
-void sw_decode_rows(int k, int n, const uint8_t* er, uint8_t* rows /* n x n */) {
-    std::memset(rows, 0, static_cast<size_t>(n) * n);
-    for (int q = 0; q < n; ++q) rows[q * n + q] = 1;  // received (or erased: the slot holds zeros)
-    uint32_t mask = 0;
-    for (int c = 0; c < n; ++c) mask |= (er[c] ? 1u : 0u) << c;
-    if (__builtin_popcount(mask) == n) return;
-    const auto rules = shared_decode_rules(n - 1, n - k, n - k);
-    const uint8_t* e = rules->entry(n, mask);
-    for (int i = 0; i < k; ++i) {
-        if (!((mask >> i) & 1u) || e[i] == 0xFF) continue;
-        std::memcpy(rows + i * n, e + k + i * n, static_cast<size_t>(n));
-    }
-}
-
 }  // namespace
 }  // namespace fec
 
@@ -1396,12 +1366,7 @@ int fec_sw_encode_1(int max_payload, int k, int n, int k2, int n2, uint8_t* cons
         // the decode (:570-573; the n flags of the window reach decodeBlock), then
         // the k data symbols reversed (:577-578)
         std::vector<uint8_t> rows(static_cast<size_t>(n) * n);
-        if (cnt > 0 && cnt < n - k + 1) {
-            sw_decode_rows(k, n, er, rows.data());
-        } else {
-            std::memset(rows.data(), 0, rows.size());
-            for (int q = 0; q < n; ++q) rows[q * n + q] = 1;
-        }
+        full_window_decode_rows(k, n, er, rows.data());
         const int npar = n2 - k2;
         const int nout = k + npar;
         const int rbA = (blocks * n + 3) & ~3, rbB = (blocks * n2 + 3) & ~3;
@@ -1463,12 +1428,7 @@ int fec_sw_decode_1(int max_payload, int k, int n, uint8_t* const* cv, const uin
         for (int i = 0; i < n; ++i) cnt += er[i] ? 1 : 0;
         if (flag) *flag = cnt >= n - k + 1 ? 1 : 0;  // :644-646
         std::vector<uint8_t> rows(static_cast<size_t>(n) * n);
-        if (cnt > 0 && cnt < n - k + 1) {
-            sw_decode_rows(k, n, er, rows.data());
-        } else {
-            std::memset(rows.data(), 0, rows.size());
-            for (int q = 0; q < n; ++q) rows[q * n + q] = 1;
-        }
+        full_window_decode_rows(k, n, er, rows.data());
         const int rb = (blocks * n + 3) & ~3;
         const size_t wbytes = static_cast<size_t>(n) * rb, cbytes = static_cast<size_t>(n) * n;
         if (int st = c.ensure(wbytes + cbytes + static_cast<size_t>(n) * blocks + 64)) return st;

@@ -54,10 +54,9 @@ int sd_relay_plan_state(int k, int n, int n2, int sdbo, const uint8_t* er, int* 
 int sd_dest_plan_state(int k, int n, int* const* header, uint8_t* rec, bool* flag);
 
 namespace {
-constexpr int kST = 10;           // T_TOT (FEC_Macro.h:32)
+constexpr int kST = kTTot;
 constexpr int kSHdr = kST + 1;    // header entries per row / header bytes per word part
 constexpr int kSSd = 3 * kST;     // codeword_vector_state_dependent rows
-constexpr int kSCycle = 1000 / 10;  // ESTIMATION_WINDOW_SIZE / ..._REDUCTION_FACTOR (FEC_Macro.h:54-55)
 constexpr int kSRow = 3344;       // an LDS row of codeword_new_vector: >= every part ((302+1)*11 = 3333)
 constexpr int kSMaxN = 11;
 
@@ -136,55 +135,6 @@ struct SymDsw {  // Decoder_Symbol_Wise (include/Decoder_Symbol_Wise.h) with ref
     }
 };
 
-struct Estimator {  // Parameter_Estimator, relay mode (T = T_TOT at every call, :72-75)
-    int T = kST, B = 0, N = 0, N_max = 0, B_cur = 0, N_cur = 0;
-    uint8_t erasure[12] = {};
-    int64_t prev = -2;
-    void estimate(int64_t seq, int msg_T) {
-        if (T == 0) return;
-        if (prev == -2) {
-            T = msg_T;
-            prev = seq - 1;
-        }
-        T = kST;
-        if (seq - prev < 1) return;
-        for (int64_t s = prev + 1; s <= seq; ++s) {
-            for (int i = T; i >= 1; --i) erasure[i] = erasure[i - 1];
-            erasure[0] = s < seq ? 1 : 0;
-            int sum = 0;
-            for (int i = 0; i <= T; ++i) sum += erasure[i] == 1;
-            if (sum == T + 1 || sum == 0) continue;
-            if (B == 0) B = 1;
-            if (N == 0) N = 1;
-            if (sum > N_max) N_max = sum;
-            int i;
-            for (i = 0; i <= T; ++i)
-                if (erasure[i]) break;
-            const int first = i;
-            for (i = T; i >= 0; --i)
-                if (erasure[i]) break;
-            const int span = i - first + 1;
-            if (span == T + 1) {
-                if (sum > N) N = B = sum;
-            } else {
-                const int mbs = std::max(sum, B), mbp = std::max(span, B);
-                if ((T - N + 1) * (T - sum + 1 + mbs) >= (T - sum + 1) * (T - N + 1 + mbp)) {
-                    if (span > B) B = N = span;
-                } else {
-                    if (sum > N) N = B = sum;
-                    if (N > B) B = N;
-                }
-            }
-            if ((T - N_max + 1) * (T - N + 1 + B) > (T - N + 1) * (T + 1)) B = N = N_max;
-        }
-        prev = seq;
-        if ((T - N_cur + 1) * (T - N + 1 + B) >= (T - N + 1) * (T - N_cur + 1 + B_cur)) {
-            B_cur = B;
-            N_cur = N;
-        }
-    }
-};
-
 struct VrdState {  // Variable_Rate_FEC_Decoder's relay / destination members
     int64_t seq_start = -1, latest = -1, sdc = -1, sde = -1;
     int T = 0, B = 0, N = 0, dcf = 0;
@@ -257,9 +207,11 @@ private:
         const uint64_t key = static_cast<uint64_t>(k) | static_cast<uint64_t>(n) << 8 | mask << 16;
         auto it = rows_memo_.find(key);
         if (it == rows_memo_.end()) {
-            uint8_t rows[kSMaxN * kSMaxN];
-            bool f;
-            decode_rows(k, n, er, rows, &f);
+            // output i = position k-1-i (symbol_wise_encode_1 :577-578, extract_data of decode_1 :647, :659)
+            uint8_t full[kSMaxN * kSMaxN], rows[kSMaxN * kSMaxN];
+            full_window_decode_rows(k, n, er, full);
+            for (int i = 0; i < k; ++i) std::memcpy(rows + i * n, full + (k - 1 - i) * n, static_cast<size_t>(n));
+            const bool f = __builtin_popcountll(mask) >= n - k + 1;
             it = rows_memo_.emplace(key, std::make_pair(intern(rows, static_cast<size_t>(k) * n), f)).first;
         }
         *flag = it->second.second;
@@ -283,26 +235,6 @@ private:
         d->lineage = next_lineage++;
         lin_calls.emplace_back();
         return d;
-    }
-    // the decode rows of a full-window decode (decodeBlock T = n-1, t = 0) for the window's flags,
-    // output i = position k-1-i (symbol_wise_encode_1 :577-578, extract_data of decode_1 :647, :659)
-    void decode_rows(int k, int n, const uint8_t* er, uint8_t* out, bool* flag) {
-        int cnt = 0;
-        uint32_t mask = 0;
-        for (int i = 0; i < n; ++i) {
-            cnt += er[i] ? 1 : 0;
-            mask |= (er[i] ? 1u : 0u) << i;
-        }
-        *flag = cnt >= n - k + 1;
-        uint8_t rows[kSMaxN * kSMaxN] = {};
-        for (int q = 0; q < n; ++q) rows[q * n + q] = 1;
-        if (cnt > 0 && cnt < n - k + 1) {
-            const auto rules = shared_decode_rules(n - 1, n - k, n - k);
-            const uint8_t* e = rules->entry(n, mask);
-            for (int i = 0; i < k; ++i)
-                if (((mask >> i) & 1u) && e[i] != 0xFF) std::memcpy(rows + i * n, e + k + i * n, static_cast<size_t>(n));
-        }
-        for (int i = 0; i < k; ++i) std::memcpy(out + i * n, rows + (k - 1 - i) * n, static_cast<size_t>(n));
     }
     // one relay object's GF call (symbol_wise_encode_1 / _state_dependent) after its slot update;
     // the part it emits goes to `out` (size bytes); type 3: its header row to *hdr
@@ -709,7 +641,8 @@ void SessionPlan::run(int relay_type, int max_payload, int64_t Q_, const uint8_t
     } v;
     uint8_t udp[12] = {}, udp2[6] = {};
     // ---- relay receiver (Application_Layer_Receiver.cpp:10-39) ----
-    std::unique_ptr<Estimator> est(new Estimator()), bg(new Estimator());
+    const auto fresh_estimator = [] { return std::make_unique<ParameterEstimator>(kST, false, true); };
+    std::unique_ptr<ParameterEstimator> est = fresh_estimator(), bg = fresh_estimator();
     int64_t cycle = 1, last_received = -1;
     bool first_call = true;
     int T_s_r = 0, N_s_r = 0, stale_counter = 0;
@@ -717,7 +650,7 @@ void SessionPlan::run(int relay_type, int max_payload, int64_t Q_, const uint8_t
     VrdState relay;
     relay.main = fresh();
     // ---- destination ----
-    std::unique_ptr<Estimator> dest(new Estimator()), dbg(new Estimator());
+    std::unique_ptr<ParameterEstimator> dest = fresh_estimator(), dbg = fresh_estimator();
     int64_t dcycle = 1;
     VrdState dst;
     dst.main.reset(new SymDsw());
@@ -832,9 +765,9 @@ void SessionPlan::run(int relay_type, int max_payload, int64_t Q_, const uint8_t
             rcount = hc;
             est->estimate(tseq, hT);
             bg->estimate(tseq, hT);
-            if (tseq + 1 > cycle * kSCycle) {  // :104-113
+            if (tseq + 1 > cycle * kEstimationCycle) {  // :104-113
                 est = std::move(bg);
-                bg.reset(new Estimator());
+                bg = fresh_estimator();
                 ++cycle;
             }
             const int k = hT - hN + 1, n = hT + 1;
@@ -846,8 +779,8 @@ void SessionPlan::run(int relay_type, int max_payload, int64_t Q_, const uint8_t
             }
             wb = relay_received(relay, tseq, hT, hB, hN, hc, n, k, n2_new, k2_new, poff);
             udp[0] = static_cast<uint8_t>(est->T);  // :176-201
-            udp[1] = static_cast<uint8_t>(est->B_cur);
-            udp[2] = static_cast<uint8_t>(est->N_cur);
+            udp[1] = static_cast<uint8_t>(est->B_current);
+            udp[2] = static_cast<uint8_t>(est->N_current);
             udp[3] = static_cast<uint8_t>(hT);
             udp[4] = static_cast<uint8_t>(hB);
             udp[5] = static_cast<uint8_t>(hN);
@@ -875,9 +808,9 @@ void SessionPlan::run(int relay_type, int max_payload, int64_t Q_, const uint8_t
             const int hT = pf.hdr8[4], hB = pf.hdr8[5], hN = pf.hdr8[6], hc = pf.hdr8[7];
             dest->estimate(tseq, hT);
             dbg->estimate(tseq, hT);
-            if (tseq + 1 > dcycle * kSCycle) {  // :251-260
+            if (tseq + 1 > dcycle * kEstimationCycle) {  // :251-260
                 dest = std::move(dbg);
-                dbg.reset(new Estimator());
+                dbg = fresh_estimator();
                 ++dcycle;
             }
             const int k = hT - hN + 1, n = hT + 1;
@@ -885,8 +818,8 @@ void SessionPlan::run(int relay_type, int max_payload, int64_t Q_, const uint8_t
                 throw std::runtime_error("session: destination call without a restatement at seq " + std::to_string(i) +
                                          " (" + std::to_string(st) + ")");
             udp2[0] = static_cast<uint8_t>(dest->T);  // :302-309
-            udp2[1] = static_cast<uint8_t>(dest->B_cur);
-            udp2[2] = static_cast<uint8_t>(dest->N_cur);
+            udp2[1] = static_cast<uint8_t>(dest->B_current);
+            udp2[2] = static_cast<uint8_t>(dest->N_current);
             udp2[3] = static_cast<uint8_t>(hT);
             udp2[4] = static_cast<uint8_t>(hB);
             udp2[5] = static_cast<uint8_t>(hN);
@@ -1011,73 +944,12 @@ __global__ __launch_bounds__(256) void ses_apply_kernel(SesDev d, const SesJob* 
     }
 }
 
-// A workgroup per lineage: codeword_new_vector's rows in LDS (logical row -> physical row map),
-// per call in order: the shift of :124-129 (rows 0..n2-2 take rows 1..n2-1, row n2-1 keeps its
-// bytes), the call's symbols into row n2-1 (type 2: data at 2 + j*n2 + i; type 3: every position),
-// type 2's parity from rows 0..n2-2 (:601-613), then row n2-1's first `size` bytes to the packet.
-__global__ __launch_bounds__(256) void ses_lineage_map_kernel(SesDev d, const SesCall* calls, const int64_t* lin,
-                                                              int64_t nlin, const uint8_t* sym) {
-    extern __shared__ uint8_t rows[];  // kSMaxN x kSRow
-    __shared__ uint8_t gexp[512];
-    __shared__ uint8_t glog[256];
-    __shared__ int map[kSMaxN];
-    for (int i = threadIdx.x; i < 512; i += 256) gexp[i] = d.gf[i];
-    glog[threadIdx.x] = d.gf[512 + threadIdx.x];
-    for (int64_t l = blockIdx.x; l < nlin; l += gridDim.x) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < kSMaxN * kSRow / 16; i += 256)
-            reinterpret_cast<uint4*>(rows)[i] = make_uint4(0, 0, 0, 0);
-        if (threadIdx.x < kSMaxN) map[threadIdx.x] = threadIdx.x;
-        __syncthreads();
-        for (int64_t ci = lin[l]; ci < lin[l + 1]; ++ci) {
-            const SesCall c = calls[ci];
-            const int n2 = c.n2, k = c.k, blocks = c.blocks;
-            __syncthreads();  // the previous call's part is stored
-            if (n2 >= 2) {
-                const int p0 = map[0];
-                const int src = map[n2 - 1];
-                __syncthreads();
-                if (threadIdx.x == 0) {
-                    for (int i = 0; i < n2 - 1; ++i) map[i] = map[i + 1];
-                    map[n2 - 1] = p0;
-                }
-                // the new row n2-1 = the old row n2-1's bytes (which is now row n2-2)
-                uint4* dst = reinterpret_cast<uint4*>(rows + p0 * kSRow);
-                const uint4* sr = reinterpret_cast<const uint4*>(rows + src * kSRow);
-                for (int i = threadIdx.x; i < kSRow / 16; i += 256) dst[i] = sr[i];
-                __syncthreads();
-            }
-            uint8_t* top = rows + map[n2 - 1] * kSRow;
-            const uint8_t* s = sym + c.d;
-            if (c.type == 3) {
-                for (int id = threadIdx.x; id < blocks * n2; id += 256) {
-                    const int j = id / n2, i = id - j * n2;
-                    top[2 + j * n2 + i] = s[j * n2 + i];
-                }
-            } else {
-                for (int id = threadIdx.x; id < blocks * k; id += 256) {
-                    const int j = id / k, i = id - j * k;
-                    top[2 + j * n2 + i] = s[j * k + i];
-                }
-                const int np = n2 - k;
-                const uint8_t* g = d.coef + c.g2;
-                for (int id = threadIdx.x; id < blocks * np; id += 256) {
-                    const int j = id / np, delta = id - j * np;
-                    uint8_t acc = 0;
-                    for (int m = 0; m < k; ++m)
-                        acc ^= gf_mul_t(gexp, glog, g[delta * k + m], rows[map[m + delta] * kSRow + 2 + j * n2 + m]);
-                    top[2 + j * n2 + n2 - 1 - delta] = acc;
-                }
-            }
-            __syncthreads();
-            uint8_t* o = d.rpk + c.out;
-            for (int x = threadIdx.x; x < c.size; x += 256) o[x] = top[x];
-        }
-    }
-}
-
-// The same walk with the map in registers: logical row i at physical row (map >> 4i) & 15, the
-// shift of :124-129 a rotation of the low n2 nibbles, computed by every thread alike (no map in
+// A workgroup per lineage: codeword_new_vector's rows in LDS, per call in order: the shift of
+// :124-129 (rows 0..n2-2 take rows 1..n2-1, row n2-1 keeps its bytes), the call's symbols into row
+// n2-1 (type 2: data at 2 + j*n2 + i; type 3: every position), type 2's parity from rows 0..n2-2
+// (:601-613), then row n2-1's first `size` bytes to the packet.
+// The logical row -> physical row map is in registers: logical row i at physical row (map >> 4i) & 15,
+// the shift a rotation of the low n2 nibbles, computed by every thread alike (no map in
 // LDS, no barrier for it; a lineage's n2 can change where copy_elements hands a new code's object
 // to the main one); the new top row keeps the old one's bytes only where the call does not write
 // them ([0, 2) and [2 + blocks*n2, hwm): every byte at or past hwm is still zero in every row); one
@@ -1420,8 +1292,8 @@ int fec_relay_session_run(fec_relay_session* h, const uint8_t* d_payload, uint8_
     const int64_t nlin = static_cast<int64_t>(p.lin.size()) - 1;
     if (nlin > 0) {
         const size_t lds = static_cast<size_t>(fec::kSMaxN) * fec::kSRow;
-        hipLaunchKernelGGL(!std::getenv("FEC_SES_LIN_MAP") ? fec::ses_lineage_kernel : fec::ses_lineage_map_kernel,
-                           dim3(static_cast<unsigned>(std::min<int64_t>(nlin, 65536))), dim3(256), lds, s, d,
+        hipLaunchKernelGGL(fec::ses_lineage_kernel, dim3(static_cast<unsigned>(std::min<int64_t>(nlin, 65536))),
+                           dim3(256), lds, s, d,
                            static_cast<const fec::SesCall*>(h->calls.p), static_cast<const int64_t*>(h->lin.p), nlin,
                            static_cast<const uint8_t*>(h->sym.p));
         FEC_HIP(hipGetLastError());

@@ -540,29 +540,24 @@ __global__ __launch_bounds__(kTThreads) void fec_sw_tile_kernel(SwTileArgs a) {
 //    symbol);
 //  * destination: output dword w of the tile's rows is gathered from the rows (4 byte reads, the
 //    (t, j, i) of its bytes stepped incrementally) and stored straight to HBM;
-//  * relay: per (row, group of 4 blocks) the 4*n1-byte span as n1+1 dword reads + v_alignbyte, and
-//    the k position words by v_perm (CT[row][m][g]); the parity words (v_perm tables of G2 in
-//    registers, parity wave-uniform); per (frame t, group g) the n2 code words transposed by v_perm
-//    into the frame's 4*n2-byte run, written as dwords to an LDS tile of 4-byte-aligned rows; then
-//    the tile is re-packed to the frame stride, 16 bytes per lane.
+//  * relay: per (row, group of 4 blocks) the 4*n1-byte span as n1+1 dword reads + v_alignbyte, the
+//    k position words by v_perm and the parity words (v_perm tables of G2), scattered into the
+//    tile's frames in LDS at the frame stride; the frames leave as 16-byte chunks
+//    (fec_sw_fast_relay2_kernel below).
 typedef uint32_t fec_v4u32 __attribute__((ext_vector_type(4)));
 constexpr int kFR = 64;          // packets per tile
 constexpr int kFT = 512;         // threads per workgroup
-constexpr int kFW = kFT / 64;    // waves
 
 constexpr int al16(int x) { return (x + 15) & ~15; }
-constexpr int cmax(int x, int y) { return x > y ? x : y; }
 
 // The whole geometry at compile time (k, n1, n2 and the payload size L): every division,
 // bound and LDS offset below is a constant.
-template <int K_, int N1_, int N2_, int L_, bool RELAY_, int TR_ = kFR, bool V2_ = false, int NT_ = kFT>
+template <int K_, int N1_, int N2_, int L_, bool RELAY_, int TR_ = kFR, int NT_ = kFT>
 struct FastGeo {
     static constexpr int K = K_, N1 = N1_, N2 = N2_, L = L_;
     static constexpr bool RELAY = RELAY_;
     static constexpr int TR = TR_;                        // packets per tile
     static constexpr int NT = NT_, NW = NT_ / 64;         // threads, waves per workgroup
-    static constexpr bool V2 = RELAY_ && V2_;             // relay: the row-scatter kernel (no CT / parity tiles)
-    static constexpr bool CT3 = RELAY && !V2;             // relay: the three-tile (CT, parity, words) kernel
     static constexpr int S = (L + 2 + K - 1) / K;        // code blocks (= sub-streams)
     static constexpr int S4 = (S + 3) & ~3, G = S4 / 4;  // CT words per position
     static constexpr int N = RELAY ? N1 : N2;            // code length of the rows read
@@ -573,21 +568,16 @@ struct FastGeo {
     static constexpr int D0 = RELAY ? N2 - 1 : 0;        // packets decoded in front of a tile
     static constexpr int ROWS = TR + H;
     static constexpr int OUT_ROW = RELAY ? F : S * K;
-    static constexpr int F4 = (F + 3) & ~3;              // LDS frame pitch
     static constexpr int ES = (K * (1 + N) + 3) & ~3;    // rule entry bytes (fec_host.h DecodeRules)
-    static constexpr int CTROW = K * S4;
     static constexpr int QCH = (16 + ROWS * STRIDE + 16 * NT - 1) / (16 * NT);  // slab chunks per thread
     static constexpr int SCH = (TR * OUT_ROW + 16 * NT - 1) / (16 * NT);      // output chunks per thread
     static constexpr int OFF_PMASK = 1552;
     static constexpr int OFF_RULE = OFF_PMASK + 4 * (TR + 64);
     static constexpr int RULE_U16 = K + K * N + 4;      // per wave
-    static constexpr int OFF_TB = al16(OFF_RULE + NW * 2 * RULE_U16);
-    static constexpr int OFF_CT = al16(OFF_TB + (CT3 ? (N2 - K) * K * 20 : 0));
-    static constexpr int OFF_OW = al16(OFF_CT + (CT3 ? ROWS * CTROW : 0));
-    static constexpr int OFF_RAW = al16(OFF_OW + (CT3 ? (N2 - K) * TR * S4 : 0));
-    static constexpr int RAWB = al16(cmax(16 + ROWS * STRIDE + 4 * N + 32, CT3 ? (TR + 1) * F4 : 0));
-    static constexpr int OFF_FR = OFF_RAW + RAWB;         // V2: the tile's frames at their own stride F
-    static constexpr int LDS = OFF_FR + (V2 ? al16(TR * F) : 0);
+    static constexpr int OFF_RAW = al16(OFF_RULE + NW * 2 * RULE_U16);
+    static constexpr int RAWB = al16(16 + ROWS * STRIDE + 4 * N + 32);
+    static constexpr int OFF_FR = OFF_RAW + RAWB;         // relay: the tile's frames at their own stride F
+    static constexpr int LDS = OFF_FR + (RELAY ? al16(TR * F) : 0);
     // waves per SIMD (the register budget of __launch_bounds__: 128 VGPRs, two workgroups per CU)
     static constexpr int WPE = 4;
     static constexpr uint32_t MDIV = static_cast<uint32_t>((uint64_t(1) << 32) / OUT_ROW + 1);
@@ -615,7 +605,6 @@ struct SwFastArgs {
     int64_t ntiles;
     int tiles_per_wg;
     uint64_t* stamps;       // diagnostics (FEC_SWDF_STAMPS): per workgroup, cycles per phase summed over tiles
-    int carry;              // carry the rows in front of a tile over from the tile before (FEC_SWDF_CARRY=0: reload)
 };
 
 // Phase clock for the diagnostics: cycles between consecutive marks, summed over the tiles.
@@ -666,7 +655,6 @@ struct FastTile {
     static constexpr int NH = GM::NH, HQ = GM::HQ;
     uint4 v[QCH];
     uint4 hc[HQ];                   // the next tile's first NH chunks (keep())
-    bool carry = false, carry_next = false;
     uint32_t f0 = 0, f1 = 0;        // flags of local rows lane and 64 + lane (next tile)
     uint64_t fb0 = 0, fb1 = 0;      // flags of local rows 0..63, 64..127 (this tile)
     int dlt = 0, dlt_next = 0;      // LDS byte of local row 0 = raw + dlt
@@ -687,7 +675,6 @@ struct FastTile {
     // the slab of rows [r0, t0+nt) (r0 = t0 - H) and the tile's flags, into registers; with cont
     // (the tile follows this workgroup's previous one) its first NH chunks come from keep() instead
     __device__ void issue(int64_t tile, bool cont) {
-        carry_next = cont;
         const int64_t t0 = tile * GM::TR, r0 = t0 - H;
         const int nt = static_cast<int>(min<int64_t>(GM::TR, a.P - t0));
         const int64_t g0 = r0 * STRIDE;                         // may be negative
@@ -724,12 +711,11 @@ struct FastTile {
     }
     __device__ uint32_t rowb(int l) const { return static_cast<uint32_t>(GM::OFF_RAW + dlt + l * STRIDE); }
     __device__ bool erased(int l) const { return ((l < 64 ? fb0 >> l : fb1 >> (l - 64)) & 1u) != 0; }
-    // the slab into LDS, the bytes of erased rows zeroed
-    __device__ void land() {
+    // the slab into LDS (carry: its first NH chunks from keep()), the bytes of erased rows zeroed
+    __device__ void land(bool carry) {
         fb0 = __ballot(f0 != 0);
         fb1 = __ballot(f1 != 0);
         dlt = dlt_next;
-        carry = carry_next;
         const bool any = (fb0 | fb1) != 0;
 #pragma unroll
         for (int q = 0; q < QCH; ++q) {
@@ -861,14 +847,14 @@ __global__ __launch_bounds__(kFT) void fec_sw_fast_dest_kernel(SwFastArgs a) {
         const int64_t t0 = tile * GM::TR;
         const int nt = static_cast<int>(min<int64_t>(GM::TR, a.P - t0));
         clk.mark(0);
-        T.land();
+        T.land(tile > tile0);
         T.masks(t0, nt);
-        if (tile + 1 < tile1) T.issue(tile + 1, a.carry != 0);
+        if (tile + 1 < tile1) T.issue(tile + 1, true);
         __syncthreads();
         clk.mark(1);
         T.decode();
         __syncthreads();
-        if (a.carry && tile + 1 < tile1) T.keep();
+        if (tile + 1 < tile1) T.keep();
         clk.mark(2);
         // output bytes of the tile's rows, 16 per lane: byte b -> row t = b / SK, o = b - t*SK,
         // j = o / K, i = o % K; LDS byte = row (t + K-1-i) of the slab, 4 + j*N + K-1-i.  A fixed
@@ -933,165 +919,9 @@ __global__ __launch_bounds__(kFT) void fec_sw_fast_dest_kernel(SwFastArgs a) {
     clk.flush(a.stamps);
 }
 
-// Relay: frame t = [size BE16][0, 0][S blocks of n2][n2-2 zeros]; block j position p =
-// XOR_m G2[k-1-m][p] * CT[t-p-n1+k][m][j] (a copy for p < k).
-template <class GM>
-__global__ __launch_bounds__(kFT, 4) void fec_sw_fast_relay_kernel(SwFastArgs a) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    constexpr int K = GM::K, N1 = GM::N1, N2 = GM::N2, S = GM::S, S4 = GM::S4, G = GM::G, H = GM::H;
-    constexpr int F = GM::F, F4 = GM::F4, CTROW = GM::CTROW;
-    constexpr int size = (S + 1) * N2;
-    FastTile<GM> T(smem, a);
-    uint32_t* tbl = reinterpret_cast<uint32_t*>(smem + GM::OFF_TB);  // [p - k][m][5] v_perm tables
-    for (int i = T.tid; i < (N2 - K) * K * 5; i += kFT) tbl[i] = a.tab[K * K * 5 + i];
-    __syncthreads();
-    const int64_t tile0 = static_cast<int64_t>(blockIdx.x) * a.tiles_per_wg;
-    const int64_t tile1 = min(tile0 + a.tiles_per_wg, a.ntiles);
-    PhaseClock clk(a.stamps != nullptr);
-    if (tile0 < tile1) T.issue(tile0, false);
-    for (int64_t tile = tile0; tile < tile1; ++tile) {
-        const int64_t t0 = tile * GM::TR;
-        const int nt = static_cast<int>(min<int64_t>(GM::TR, a.P - t0));
-        clk.mark(0);
-        T.land();
-        T.masks(t0, nt);
-        if (tile + 1 < tile1) T.issue(tile + 1, a.carry != 0);
-        __syncthreads();
-        clk.mark(1);
-        T.decode();
-        __syncthreads();
-        if (a.carry && tile + 1 < tile1) T.keep();
-        clk.mark(2);
-        // CT[l][m][g] from the (decoded) rows: a lane per (row, group of 4 blocks); only the rows
-        // a frame of the tile reads (local rows >= k-1)
-        for (int it = T.tid; it < (H + nt - (K - 1)) * G; it += kFT) {
-            const int l = K - 1 + it / G, g = it % G;
-            const uint32_t sb = T.rowb(l) + 4 * g * N1;
-            uint32_t d[N1 + 1];
-            const uint32_t ab = sb & ~3u;
-#pragma unroll
-            for (int q = 0; q <= N1; ++q) d[q] = *reinterpret_cast<const uint32_t*>(smem + ab + 4 * q);
-            align_words(d, static_cast<int>(sb & 3));
-            const uint32_t cb = GM::OFF_CT + l * CTROW + 4 * g;
-#pragma unroll
-            for (int m = 0; m < K; ++m)
-                *reinterpret_cast<uint32_t*>(smem + cb + m * S4) = gather4(d, m, N1 + m, 2 * N1 + m, 3 * N1 + m);
-        }
-        __syncthreads();
-        clk.mark(3);
-        // parity words OW[p-k][t][g] = XOR_m G2[k-1-m][p] * CT[t-p-n1+k][m][g]: 64-item blocks with
-        // p wave-uniform, the 5k v_perm tables of p in registers (reloaded when p changes)
-        {
-            const int NBk = (nt * G + 63) >> 6;
-            const int nb = (N2 - K) * NBk, per = (nb + kFW - 1) / kFW;  // a contiguous run of blocks per wave
-            int cur_p = -1;
-            uint32_t tt[K][5];
-            for (int ib = T.wave * per; ib < min(nb, (T.wave + 1) * per); ++ib) {
-                const int pi = ib / NBk;  // wave-uniform
-                const int p = K + pi;
-                const int item = (ib - pi * NBk) * 64 + T.lane;
-                if (p != cur_p) {
-#pragma unroll
-                    for (int m = 0; m < K; ++m)
-#pragma unroll
-                        for (int q = 0; q < 5; ++q) tt[m][q] = tbl[(pi * K + m) * 5 + q];
-                    cur_p = p;
-                }
-                if (item >= nt * G) continue;
-                const int t = item / G, g = item - t * G;
-                const uint32_t src = GM::OFF_CT + (H + t - p - N1 + K) * CTROW + 4 * g;  // local row t-p-n1+k
-                uint32_t x[K];
-#pragma unroll
-                for (int m = 0; m < K; ++m) x[m] = *reinterpret_cast<const uint32_t*>(smem + src + m * S4);
-                uint32_t w = 0;
-#pragma unroll
-                for (int m = 0; m < K; ++m) w ^= gf_mul4x(tt[m], x[m]);
-                *reinterpret_cast<uint32_t*>(smem + GM::OFF_OW + (pi * kFR + t) * S4 + 4 * g) = w;
-            }
-        }
-        __syncthreads();
-        clk.mark(4);
-        // frame words of (t, g) -> the frame's 4*n2-byte run for blocks 4g..4g+3 in LDS rows of F4
-        // (the rows' space: free once CT is built); group 0 also writes the header, the last group
-        // the zero tail up to F4
-        for (int it = T.tid; it < nt * G; it += kFT) {
-            const int t = it / G, g = it % G;
-            uint32_t W[N2];
-#pragma unroll
-            for (int p = 0; p < N2; ++p) {
-                if (p < K)
-                    W[p] = *reinterpret_cast<const uint32_t*>(smem + GM::OFF_CT + (H + t - p - N1 + K) * CTROW +
-                                                              (K - 1 - p) * S4 + 4 * g);
-                else
-                    W[p] = *reinterpret_cast<const uint32_t*>(smem + GM::OFF_OW + ((p - K) * kFR + t) * S4 + 4 * g);
-            }
-            const uint32_t ob = GM::OFF_RAW + t * F4 + 4 + 4 * g * N2;
-            const int lim = N2 * min(4, S - 4 * g);  // run bytes that are blocks < S
-#pragma unroll
-            for (int q = 0; q < N2; ++q) {
-                // byte y = 4q + x of the run: block y / N2, position y % N2 = byte (y / N2) of W[y % N2]
-                const int y0 = 4 * q, y1 = 4 * q + 1, y2 = 4 * q + 2, y3 = 4 * q + 3;
-                uint32_t val = gather4(W, 4 * (y0 % N2) + y0 / N2, 4 * (y1 % N2) + y1 / N2,
-                                       4 * (y2 % N2) + y2 / N2, 4 * (y3 % N2) + y3 / N2);
-                val &= keep_bytes(lim - 4 * q);  // the blocks' end: the tail's zeros from there
-                if (4 + 4 * g * N2 + 4 * q + 4 <= F4) *reinterpret_cast<uint32_t*>(smem + ob + 4 * q) = val;
-            }
-            if (g == 0) *reinterpret_cast<uint32_t*>(smem + GM::OFF_RAW + t * F4) = uint32_t(size >> 8) | (uint32_t(size & 255) << 8);
-            if (g == G - 1)  // the tail's zero dwords after the run
-                for (int o = 4 + 4 * G * N2; o + 4 <= F4; o += 4) *reinterpret_cast<uint32_t*>(smem + GM::OFF_RAW + t * F4 + o) = 0;
-        }
-        __syncthreads();
-        clk.mark(5);
-        // re-pack rows of F4 to the frame stride F, 16 bytes per lane (t0*F is a multiple of 16); a
-        // fixed number of buffer stores per lane
-        const int obytes = nt * F;
-        uint8_t* gout = a.out + t0 * F;
-        const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(gout, 0, obytes & ~15, 0x00020000);
-#pragma unroll
-        for (int qq = 0; qq < GM::SCH; ++qq) {
-            asm volatile("" ::: "memory");  // one chunk's reads at a time (registers)
-            const int w = T.tid + qq * kFT;
-            const uint32_t b = 16 * w;
-            uint32_t val[4] = {0, 0, 0, 0};
-            if (static_cast<int>(b) < obytes) {
-                int t = static_cast<int>(b / F);
-                int o = static_cast<int>(b) - t * F;
-#pragma unroll 1
-                for (int q = 0; q < 4; ++q) {
-                    const uint32_t s0 = GM::OFF_RAW + t * F4 + o;
-                    const uint32_t d0 = *reinterpret_cast<const uint32_t*>(smem + (s0 & ~3u));
-                    const uint32_t d1 = *reinterpret_cast<const uint32_t*>(smem + (s0 & ~3u) + 4);
-                    uint32_t v = __builtin_amdgcn_alignbyte(d1, d0, s0 & 3u);
-                    const int kk = F - o;  // bytes of frame t in this dword
-                    if (kk < 4) {
-                        const uint32_t e0 = *reinterpret_cast<const uint32_t*>(smem + GM::OFF_RAW + (t + 1) * F4);
-                        v = (v & ((1u << (8 * kk)) - 1u)) | (e0 << (8 * kk));
-                    }
-                    val[0] = val[1];  // shifted in: val[3] is this dword after four
-                    val[1] = val[2];
-                    val[2] = val[3];
-                    val[3] = v;
-                    o += 4;
-                    if (o >= F) {
-                        o -= F;
-                        ++t;
-                    }
-                }
-            }
-            const uint32_t so = static_cast<int>(b) + 16 <= obytes ? b : 0x7ffffff0u;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(fec_v4u32, make_uint4(val[0], val[1], val[2], val[3])), ro, so, 0, 0);
-            if (static_cast<int>(b) < obytes && static_cast<int>(b) + 16 > obytes)  // the output's ragged end
-                for (int x = 0; static_cast<int>(b) + x < obytes; ++x) gout[b + x] = uint8_t(val[x >> 2] >> (8 * (x & 3)));
-        }
-        __syncthreads();
-        clk.mark(6);
-    }
-    clk.flush(a.stamps);
-}
-
-// Relay, row scatter: frame t block j position p depends on one (decoded) row only, row
-// t - p - n1 + k: its data symbols m of block j (p < k: symbol k-1-p; p >= k: XOR_m G2[k-1-m][p] *
-// symbol m).  A lane per (row, group of 4 blocks) reads the row's 4*n1-byte span once (n1+1 dword
+// Relay: frame t = [size BE16][0, 0][S blocks of n2][n2-2 zeros].  Row scatter: frame t block j
+// position p depends on one (decoded) row only, row t - p - n1 + k: its data symbols m of block j
+// (p < k: symbol k-1-p; p >= k: XOR_m G2[k-1-m][p] * symbol m).  A lane per (row, group of 4 blocks) reads the row's 4*n1-byte span once (n1+1 dword
 // reads + v_alignbyte), forms the k symbol words by v_perm, the n2-k parity words with the G2
 // tables in scalar registers, and writes each position's 4 bytes straight into the frames of the
 // tile, laid out in LDS at their own stride F (one base address, every byte at a compile-time
@@ -1115,14 +945,14 @@ __global__ __launch_bounds__(GM::NT, GM::WPE) void fec_sw_fast_relay2_kernel(SwF
         const int64_t t0 = tile * TR;
         const int nt = static_cast<int>(min<int64_t>(TR, a.P - t0));
         clk.mark(0);
-        T.land();
+        T.land(tile > tile0);
         T.masks(t0, nt);
-        if (tile + 1 < tile1) T.issue(tile + 1, a.carry != 0);
+        if (tile + 1 < tile1) T.issue(tile + 1, true);
         __syncthreads();
         clk.mark(1);
         T.decode();
         __syncthreads();
-        if (a.carry && tile + 1 < tile1) T.keep();
+        if (tile + 1 < tile1) T.keep();
         clk.mark(2);
         // rows k-1 .. k-1 + nt+n2-2 feed the tile's frames: row k-1+r, position p -> frame r-(n2-1)+p.
         // Interior rows (r in [n2-1, nt)) reach a frame of the tile at every position; with a full
@@ -1165,14 +995,10 @@ __global__ __launch_bounds__(GM::NT, GM::WPE) void fec_sw_fast_relay2_kernel(SwF
                         }
                     }
                     uint8_t* dst = smem + fb + p * (F + 1);
-#ifdef FEC_RELAY2_ABLATE_WRITES  // diagnostic build only (wrong output): one byte write per position
-                    dst[0] = static_cast<uint8_t>(w ^ (w >> 8) ^ (w >> 16) ^ (w >> 24));
-#else
                     dst[0] = static_cast<uint8_t>(w);
                     if (!CHK || nb > 1) dst[N2] = static_cast<uint8_t>(w >> 8);
                     if (!CHK || nb > 2) dst[2 * N2] = static_cast<uint8_t>(w >> 16);
                     if (!CHK || nb > 3) dst[3 * N2] = static_cast<uint8_t>(w >> 24);
-#endif
                 }
             });
         };
@@ -1256,6 +1082,47 @@ int grid_for(int64_t items) {
     return static_cast<int>(std::min<int64_t>((items + fec::kSwThreads - 1) / fec::kSwThreads, 8192));
 }
 
+// Blocks of `kern` resident per CU (registers and LDS both limit them), at least 1.
+int blocks_per_cu(const void* kern, int threads, size_t lds) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, threads, lds) != hipSuccess || n < 1) n = 1;
+    return n;
+}
+
+// One wave of resident workgroups, each walking a contiguous run of tiles: the grid, and the run's
+// length to *tiles_per_wg.
+unsigned resident_grid(int per_cu, int64_t ntiles, int* tiles_per_wg) {
+    static const int cus = [] {
+        int dev = 0, c = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 1)
+            c = 256;
+        return c;
+    }();
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(ntiles, int64_t(cus) * per_cu));
+    *tiles_per_wg = static_cast<int>((ntiles + grid - 1) / grid);
+    return static_cast<unsigned>((ntiles + *tiles_per_wg - 1) / *tiles_per_wg);
+}
+
+// Diagnostics (FEC_SWDF_STAMPS): the workgroups' phase stamps back (synchronises the stream), mean
+// cycles per tile of each of the `phases` (named in `what`) to stderr.
+hipError_t print_stamps(const uint64_t* stamps, unsigned grid, int64_t ntiles, int phases, hipStream_t s,
+                        const char* kernel, bool relay, int K, int tiles_per_wg, long long lds, int tile, const char* what) {
+    std::vector<uint64_t> h(static_cast<size_t>(grid) * 8);
+    hipError_t e = hipMemcpyAsync(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return e;
+    std::fprintf(stderr, "FEC_SWDF_STAMPS %s %s K=%d grid=%u tiles/wg=%d lds=%lld: cycles per tile of %d: %s", kernel,
+                 relay ? "relay" : "dest", K, grid, tiles_per_wg, lds, tile, what);
+    for (int k = 0; k < phases; ++k) {
+        double sum = 0;
+        for (unsigned b = 0; b < grid; ++b) sum += static_cast<double>(h[b * 8 + k]);
+        std::fprintf(stderr, " %.0f", sum / static_cast<double>(ntiles));
+    }
+    std::fprintf(stderr, "\n");
+    return hipSuccess;
+}
+
 // The tiled kernel for k = K (template) when its LDS fits 64 KB; false = not launched (the
 // per-(packet, block) kernels below run instead).
 template <bool RELAY>
@@ -1278,23 +1145,9 @@ bool launch_tile(int K, fec::SwTileArgs a, hipStream_t s, hipError_t* err) {
     const int64_t lds = a.off_raw + ((rawb + 15) & ~int64_t(15));
     if (lds > 65536) return false;
     a.ntiles = (a.P + kTR - 1) / kTR;
-    // one wave of resident workgroups (registers and LDS both limit them), each walking a
-    // contiguous run of tiles
     auto launch = [&](auto kern) {
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, fec::kTThreads, static_cast<size_t>(lds)) !=
-                hipSuccess || per_cu < 1)
-            per_cu = 1;
-        static const int cus = [] {
-            int dev = 0, c = 0;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 1)
-                c = 256;
-            return c;
-        }();
-        const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(a.ntiles, int64_t(cus) * per_cu));
-        a.tiles_per_wg = static_cast<int>((a.ntiles + grid - 1) / grid);
-        const unsigned g = static_cast<unsigned>((a.ntiles + a.tiles_per_wg - 1) / a.tiles_per_wg);
+        const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(kern), fec::kTThreads, static_cast<size_t>(lds));
+        const unsigned g = resident_grid(per_cu, a.ntiles, &a.tiles_per_wg);
         hipLaunchKernelGGL(kern, dim3(g), dim3(fec::kTThreads), static_cast<size_t>(lds), s, a);
         return g;
     };
@@ -1312,21 +1165,9 @@ bool launch_tile(int K, fec::SwTileArgs a, hipStream_t s, hipError_t* err) {
     }
 #undef FEC_SW_TILE_CASE
     *err = hipGetLastError();
-    if (a.stamps && *err == hipSuccess) {
-        // diagnostics: mean cycles per tile of each phase over the workgroups
-        std::vector<uint64_t> h(static_cast<size_t>(g) * 8);
-        *err = hipMemcpyAsync(h.data(), a.stamps, h.size() * 8, hipMemcpyDeviceToHost, s);
-        if (*err == hipSuccess) *err = hipStreamSynchronize(s);
-        double sum[5] = {0, 0, 0, 0, 0};
-        for (unsigned b = 0; b < g; ++b)
-            for (int k = 0; k < 5; ++k) sum[k] += static_cast<double>(h[b * 8 + k]);
-        const double tiles = static_cast<double>(a.ntiles);
-        std::fprintf(stderr,
-                     "FEC_SWDF_STAMPS %s K=%d grid=%u tiles/wg=%d lds=%lld: cycles per tile: stage %.0f, masks+CT %.0f, "
-                     "decode %.0f, output %.0f, store %.0f\n",
-                     RELAY ? "relay" : "dest", K, g, a.tiles_per_wg, static_cast<long long>(lds), sum[0] / tiles,
-                     sum[1] / tiles, sum[2] / tiles, sum[3] / tiles, sum[4] / tiles);
-    }
+    if (a.stamps && *err == hipSuccess)
+        *err = print_stamps(a.stamps, g, a.ntiles, 5, s, "tile", RELAY, K, a.tiles_per_wg, static_cast<long long>(lds), kTR,
+                            "stage/masks+CT/decode/output/store");
     return true;
 }
 
@@ -1341,17 +1182,14 @@ uint64_t* stamps_buffer() {  // FEC_SWDF_STAMPS set: a device buffer for the pha
 }
 
 // The specialised kernels: n1 = n2 = 11 (T = 10, the T_TOT family of every adaptive tuple),
-// k = 7..11, L = 300 (the reference's packet payload), every block relayed (blocks == S), input
+// k = 4..11, L = 300 (the reference's packet payload), every block relayed (blocks == S), input
 // rows at the code's own width, 16-byte aligned input, 4-byte aligned output.
 constexpr int kFastN = 11, kFastL = 300;
 
 template <class GM>
 bool launch_fast_geo(fec::SwFastArgs a, hipStream_t s, hipError_t* err) {
-    constexpr int kFT = GM::NT;
-    constexpr int kFR = GM::TR;
     auto kern = [] {
-        if constexpr (GM::V2) return fec::fec_sw_fast_relay2_kernel<GM>;
-        else if constexpr (GM::RELAY) return fec::fec_sw_fast_relay_kernel<GM>;
+        if constexpr (GM::RELAY) return fec::fec_sw_fast_relay2_kernel<GM>;
         else return fec::fec_sw_fast_dest_kernel<GM>;
     }();
     constexpr int lds = GM::LDS;
@@ -1360,74 +1198,28 @@ bool launch_fast_geo(fec::SwFastArgs a, hipStream_t s, hipError_t* err) {
         lds <= 65536 || hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
     if (!attr_ok) return false;
-    static const int per_cu = [&] {
-        int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, kFT, static_cast<size_t>(lds)) != hipSuccess || n < 1)
-            n = 1;
-        return n;
-    }();
-    static const int cus = [] {
-        int dev = 0, c = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 1)
-            c = 256;
-        return c;
-    }();
-    a.ntiles = (a.P + kFR - 1) / kFR;
-    // one wave of resident workgroups, each walking a contiguous run of tiles
-    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(a.ntiles, int64_t(cus) * per_cu));
-    a.tiles_per_wg = static_cast<int>((a.ntiles + grid - 1) / grid);
-    const unsigned g = static_cast<unsigned>((a.ntiles + a.tiles_per_wg - 1) / a.tiles_per_wg);
-    hipLaunchKernelGGL(kern, dim3(g), dim3(kFT), static_cast<size_t>(lds), s, a);
+    static const int per_cu = blocks_per_cu(reinterpret_cast<const void*>(kern), GM::NT, static_cast<size_t>(lds));
+    a.ntiles = (a.P + GM::TR - 1) / GM::TR;
+    const unsigned g = resident_grid(per_cu, a.ntiles, &a.tiles_per_wg);
+    hipLaunchKernelGGL(kern, dim3(g), dim3(GM::NT), static_cast<size_t>(lds), s, a);
     *err = hipGetLastError();
-    if (a.stamps && *err == hipSuccess) {
-        std::vector<uint64_t> h(static_cast<size_t>(g) * 8);
-        *err = hipMemcpyAsync(h.data(), a.stamps, h.size() * 8, hipMemcpyDeviceToHost, s);
-        if (*err == hipSuccess) *err = hipStreamSynchronize(s);
-        double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (unsigned b = 0; b < g; ++b)
-            for (int k = 0; k < 8; ++k) sum[k] += static_cast<double>(h[b * 8 + k]);
-        const double tl = static_cast<double>(a.ntiles);
-        std::fprintf(stderr,
-                     "FEC_SWDF_STAMPS fast %s K=%d grid=%u tiles/wg=%d lds=%d: cycles per tile of %d: %s %.0f %.0f %.0f "
-                     "%.0f %.0f %.0f\n",
-                     GM::RELAY ? "relay" : "dest", GM::K, g, a.tiles_per_wg, lds, kFR,
-                     GM::V2 ? "land+masks/decode/scatter/store" : GM::RELAY ? "land+masks/decode/CT/parity/words/store"
-                                                                       : "land+masks/decode/out",
-                     sum[0] / tl,
-                     sum[1] / tl, sum[2] / tl, sum[3] / tl, sum[4] / tl, sum[5] / tl);
-    }
+    if (a.stamps && *err == hipSuccess)
+        *err = print_stamps(a.stamps, g, a.ntiles, GM::RELAY ? 4 : 3, s, "fast", GM::RELAY, GM::K, a.tiles_per_wg, lds, GM::TR,
+                            GM::RELAY ? "land+masks/decode/scatter/store" : "land+masks/decode/out");
     return true;
 }
 
-// The relay's kernel: the row scatter (default; tiles of 64 packets for k >= 7, of 32 / 16 for the
-// longer rows of k = 5..6 / 4, 512 threads), or FEC_SWDF_RELAY=3 round 5's three-tile kernel (k >= 7,
-// kept for A/B).
-int relay_variant() {
-    static const int v = [] {
-        const char* r = std::getenv("FEC_SWDF_RELAY");
-        return (r && r[0] == '3') ? 0 : 1;
-    }();
-    return v;
-}
-
+// The relay's tile is 64 packets for k >= 7, 32 / 16 for the longer rows of k = 5..6 / 4 (512 threads).
 template <bool RELAY>
 bool launch_fast(int K, fec::SwFastArgs a, int L, int n1, int n2, int blocks, int S, int64_t stride, hipStream_t s,
                  hipError_t* err) {
     if (L != kFastL || n2 != kFastN || (RELAY && n1 != kFastN) || blocks != S) return false;
     if ((reinterpret_cast<uintptr_t>(a.in) & 15) || (reinterpret_cast<uintptr_t>(a.out) & 3)) return false;
-    const int rv = RELAY ? relay_variant() : 0;
-#define FEC_SW_FAST_CASE(KK)                                                                      \
-    case KK: {                                                                                    \
-        using GM = fec::FastGeo<KK, kFastN, kFastN, kFastL, RELAY>;                                \
-        if (stride != GM::STRIDE) return false;                                                   \
-        if constexpr (RELAY) {                                                                    \
-            if (rv) return launch_fast_geo<fec::FastGeo<KK, kFastN, kFastN, kFastL, true, (KK >= 7 ? 64 : KK >= 5 ? 32 : 16), true>>(a, s, err); \
-            if constexpr (KK < 7) return false;                                                   \
-            else return launch_fast_geo<GM>(a, s, err);                                           \
-        } else {                                                                                  \
-            return launch_fast_geo<GM>(a, s, err);                                                \
-        }                                                                                         \
+#define FEC_SW_FAST_CASE(KK)                                                                                          \
+    case KK: {                                                                                                        \
+        using GM = fec::FastGeo<KK, kFastN, kFastN, kFastL, RELAY, (!RELAY || KK >= 7 ? 64 : KK >= 5 ? 32 : 16)>;    \
+        if (stride != GM::STRIDE) return false;                                                                       \
+        return launch_fast_geo<GM>(a, s, err);                                                                        \
     }
     switch (K) {
         FEC_SW_FAST_CASE(4) FEC_SW_FAST_CASE(5) FEC_SW_FAST_CASE(6)
@@ -1435,32 +1227,6 @@ bool launch_fast(int K, fec::SwFastArgs a, int L, int n1, int n2, int blocks, in
         default: return false;
     }
 #undef FEC_SW_FAST_CASE
-}
-
-bool fast_enabled() {
-    static const bool on = [] {
-        const char* v = std::getenv("FEC_SWDF_FAST");
-        return !(v && v[0] == '0');
-    }();
-    return on;
-}
-
-// the specialised kernels carry a tile's front rows over from the workgroup's previous tile
-// (FEC_SWDF_CARRY=0: every tile reloads them from HBM)
-bool carry_enabled() {
-    static const bool on = [] {
-        const char* v = std::getenv("FEC_SWDF_CARRY");
-        return !(v && v[0] == '0');
-    }();
-    return on;
-}
-
-bool tiles_enabled() {
-    static const bool on = [] {
-        const char* v = std::getenv("FEC_SWDF_TILE");
-        return !(v && v[0] == '0');
-    }();
-    return on;
 }
 
 int launch_diag_decode(const fec::CodecView& v, int blocks, const uint8_t* in, int64_t in_stride, int in_off,
@@ -1544,7 +1310,7 @@ int fec_swdf_relay_batch(fec_swdf* w, const uint8_t* d_cw, int64_t cw_stride, co
     if (P == 0) return FEC_OK;
     if (!d_cw || !d_erasure || !d_frames || cw_stride < w->v1.S * w->v1.n) return FEC_ERR_ARG;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (fast_enabled() && w->v1.wbase_n >= 0) {
+    if (w->v1.wbase_n >= 0) {
         if (!w->d_tab) {
             // v_perm tables of G2[k-1-m][p] (fec_device.h gf_mul4x): c*{0..7}, c*({0..7}<<3), c*({0..3}<<6)
             const int k = w->v2.k, n2 = w->v2.n;
@@ -1565,7 +1331,6 @@ int fec_swdf_relay_batch(fec_swdf* w, const uint8_t* d_cw, int64_t cw_stride, co
             FEC_HIP(hipMemcpy(w->d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         }
         fec::SwFastArgs a{};
-        a.carry = carry_enabled() ? 1 : 0;
         a.in = d_cw;
         a.er = d_erasure;
         a.P = P;
@@ -1579,7 +1344,7 @@ int fec_swdf_relay_batch(fec_swdf* w, const uint8_t* d_cw, int64_t cw_stride, co
         if (launch_fast<true>(w->v1.k, a, w->v1.L, w->v1.n, w->v2.n, w->blocks, w->v1.S, cw_stride, s, &e))
             return e == hipSuccess ? FEC_OK : FEC_ERR_HIP;
     }
-    if (tiles_enabled() && w->v1.wbase_n >= 0) {
+    if (w->v1.wbase_n >= 0) {
         // decode + re-encode in one pass over the codewords (no workspace)
         fec::SwTileArgs a{};
         a.in = d_cw;
@@ -1630,9 +1395,8 @@ int fec_swdf_destination_batch(fec_swdf* w, const uint8_t* d_frames, const uint8
     if (P == 0) return FEC_OK;
     if (!d_frames || !d_erasure || !d_out) return FEC_ERR_ARG;
     // frame symbol (j, m) at byte 4 + j*n2 + m (size header + codeword_new_vector's offset 2)
-    if (fast_enabled() && w->v2.wbase_n >= 0) {
+    if (w->v2.wbase_n >= 0) {
         fec::SwFastArgs a{};
-        a.carry = carry_enabled() ? 1 : 0;
         a.in = d_frames;
         a.er = d_erasure;
         a.P = P;
@@ -1646,7 +1410,7 @@ int fec_swdf_destination_batch(fec_swdf* w, const uint8_t* d_frames, const uint8
                                static_cast<hipStream_t>(stream), &e))
             return e == hipSuccess ? FEC_OK : FEC_ERR_HIP;
     }
-    if (tiles_enabled() && w->v2.wbase_n >= 0) {
+    if (w->v2.wbase_n >= 0) {
         fec::SwTileArgs a{};
         a.in = d_frames;
         a.in_stride = w->F;

@@ -68,6 +68,7 @@ void ParameterEstimator::estimate(int64_t seq, int msg_T) {
         T = msg_T;
         previous_win_end = seq - 1;
     }
+    if (relay_mode) T = kTTot;  // (:72-75)
     const int64_t current_win_end = seq;
     if (current_win_end - previous_win_end < 1) return;  // out of order (:84-86)
     const uint32_t wmask = (T + 1 >= 32) ? 0xffffffffu : ((1u << (T + 1)) - 1u);
@@ -139,8 +140,6 @@ const DecodeRules& VrPlan::rules_for(int T, int B, int N) {
 
 namespace {
 
-constexpr int kTTot = 10;                 // T_TOT (FEC_Macro.h:32)
-
 // The plan's own threads (feedback producer, decoder workers), and the calling thread for the
 // control loop, run on the 8 CPUs of the calling thread's aligned group (within the process's
 // allowed set), so that what the producer writes and the control loop reads stays near: on a
@@ -179,8 +178,6 @@ int vr_allowed_cpus() {
     if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return static_cast<int>(std::thread::hardware_concurrency());
     return std::max(1, CPU_COUNT(&allowed));
 }
-constexpr int kEstimationCycle = 1000 / 10;  // ESTIMATION_WINDOW_SIZE / ..._REDUCTION_FACTOR (:54-55)
-
 struct Report {        // decoder instance `id` reports packet x at its call for seq
     int64_t seq, x;
 };

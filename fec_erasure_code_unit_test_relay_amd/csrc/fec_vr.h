@@ -37,13 +37,16 @@ struct fec_vr_plan;  // the C ABI's plan handle (fec_vr.cpp)
 
 namespace fec {
 
-// Parameter_Estimator (src/Parameter_Estimator.cpp:21-223), RELAYING_TYPE 0.
+// Parameter_Estimator (src/Parameter_Estimator.cpp:21-223): RELAYING_TYPE 0, or with `relay` the
+// estimators of RELAYING_TYPE 2 / 3, whose window is T_TOT + 1 flags at every call (:72-75).
 struct ParameterEstimator {
     bool adaptive_mode_MDS = false;
+    bool relay_mode = false;
     int T = 0, B = 0, N = 0, N_max = 0, B_current = 0, N_current = 0;
     uint32_t erasure = 0;  // bit i = the reference's erasure[i] (window of T+1 flags, newest at 0)
     int64_t previous_win_end = -2;
-    ParameterEstimator(int T_value, bool mds) : adaptive_mode_MDS(mds), T(T_value) {}
+    ParameterEstimator(int T_value, bool mds, bool relay = false)
+        : adaptive_mode_MDS(mds), relay_mode(relay), T(T_value) {}
     void estimate(int64_t seq, int msg_T);
     void make_MDS_estimates();
     // estimate(seq, T) for the next in-order seq would change nothing but previous_win_end: the

@@ -263,7 +263,11 @@ def test_sd_tile_kernel_fallback_geometry():
 @pytest.mark.parametrize("cfg", SD_CASES)
 def test_gpu_sdswdf_bit_exact_vs_oracle(cfg, pi):
     """HIP relay frames, destination data_with_header rows and flags per seq against the oracle, on
-    three shipped recordings; erased rows and frames are filled with garbage (never read)."""
+    three shipped recordings; erased rows and frames are filled with garbage (never read).
+
+    The kernel tier of each case follows from its shape alone (fec_sdswdf.hip sd_tile_fit):
+    (10,3,10,3), (10,5,8,3), (10,1,10,1) and (10,4,10,4) take the type-3 tile kernel on both legs;
+    (10,3,9,2) and (6,2,5,1), which have no tile instantiation, the per-(packet, block) kernel."""
     torch = pytest.importorskip("torch")
     import fec_erasure_code_unit_test_relay_amd as fec
     from fec_erasure_code_unit_test_relay_amd.relay import StateDependentRelay

@@ -17,7 +17,6 @@ SEED = 0x5EED
 SWDF_CASES = [(10, 3, 10, 3), (10, 3, 9, 2), (10, 1, 12, 3), (10, 10, 10, 10), (10, 5, 8, 3), (6, 2, 10, 6)]
 
 
-
 def source_dwh(P, S, k):
     src = oracle.fill_payload(0, P, L, SEED)
     d = np.zeros((P, S * k), dtype=np.uint8)
@@ -57,23 +56,42 @@ def test_oracle_swdf_corrects_within_both_hops():
     assert r2["relay_flag"].sum() > 0
 
 
+# (cfg, payload size) of the GPU comparison; the ids of the L = 300 cases are those of SWDF_CASES alone.
+# L = 1000 with (10, 3, 10, 3): k = 8, S = 126, codeword stride 1386, frame 1399 bytes.  The
+# specialised kernels take L = 300 only, and a tile's staged slab (relay 16 + 52 * 1386 = 72 088
+# bytes, destination 16 + 42 * 1399 = 58 774) is over the tile kernel's 16 * 256 * 8 = 32 768 bytes of
+# chunks, so both legs run the per-(packet, block) kernels.
+SWDF_GPU_CASES = [(cfg, L) for cfg in SWDF_CASES] + [((10, 3, 10, 3), 1000)]
+SWDF_GPU_IDS = ["cfg%d" % i for i in range(len(SWDF_CASES))] + ["cfg0-L1000"]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("cfg", SWDF_CASES)
-def test_gpu_swdf_bit_exact_vs_oracle(cfg):
+@pytest.mark.parametrize("cfg,payload", SWDF_GPU_CASES, ids=SWDF_GPU_IDS)
+def test_gpu_swdf_bit_exact_vs_oracle(cfg, payload):
     """Relay frames, relay flags, destination data_with_header rows and destination flags per seq,
     against the oracle, with hop 1 = bin/erasure.bin and hop 2 = bin/erasure2.bin (the
-    reference's two shipped Fritchman recordings), windows chosen to contain bursts."""
+    reference's two shipped Fritchman recordings), windows chosen to contain bursts.
+
+    The kernel tier of each case follows from its shape alone (fec_swdf.hip).  At L = 300:
+    (10,3,10,3) the specialised kernels on both legs; (10,3,9,2), (10,1,12,3) and (10,5,8,3) the
+    runtime-K tile kernel on both; (6,2,10,6) the tile kernel at the relay (n1 = 7) and the
+    specialised kernel at the destination; (10,10,10,10) (k = 1, S = 302: rows of 3 322 / 3 335
+    bytes, a slab past the tile kernel's chunks) and the L = 1000 case the per-(packet, block)
+    kernels on both."""
     torch = pytest.importorskip("torch")
     import fec_erasure_code_unit_test_relay_amd as fec
     from fec_erasure_code_unit_test_relay_amd.relay import SymbolWiseRelay
     T1, N1, T2, N2 = cfg
-    P = 6000
+    L = payload
+    P = 6000 if L == 300 else 600
     e1 = load_pattern("bin_erasure")[3000:3000 + P].copy()
     e2 = load_pattern("bin_erasure2")[9000:9000 + P].copy()
     e1[[0, 1, 2, 3, 500, 501, 503, 505, 507]] = 1  # start-up and dense windows
-    e2[[5, 6, 900, 902, 904, 906]] = 1
+    e2[[5, 6, 900, 902, 904, 906] if P == 6000 else [5, 6, 400, 402, 404, 406]] = 1
     ref = oracle.swdf_run(L, *cfg, P, e1, e2, seed=SEED)
     assert ref["relay_flag"].sum() > 0 or ref["dest_flag"].sum() > 0 or cfg[1] >= 3
+    if L == 1000:  # both failure paths
+        assert ref["frames"].shape == (P, 1399) and ref["relay_flag"].sum() == 60 and ref["dest_flag"].sum() == 41
     torch.cuda.set_device(0)
     c = fec.Codec(L, T1, N1, N1)
     cw, _ = c.encode(fec.fill_payload(0, P, L, SEED))
