@@ -70,6 +70,7 @@ def lib() -> ctypes.CDLL:
     L.fec_codec_geometry.argtypes = [vp, ip, ip, ip, ip]
     L.fec_codec_generator.argtypes = [vp, vp]
     L.fec_codec_set_encode_path.argtypes = [vp, i32]
+    L.fec_encode_tile_fetch.argtypes = [i32, i32, i32, i32, i32, ip, ip, ip, ip]
     L.fec_codec_set_copy_path.argtypes = [vp, i32]
     L.fec_codec_set_plan_path.argtypes = [vp, i32]
     L.fec_codec_info.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
@@ -163,7 +164,7 @@ def lib() -> ctypes.CDLL:
                  "fec_relay_vr_destroy", "fec_relay_vr_geometry", "fec_relay_vr_run",
                  "fec_swdf_create", "fec_swdf_destroy", "fec_swdf_geometry", "fec_swdf_relay_batch",
                  "fec_swdf_destination_batch", "fec_codec_create", "fec_codec_destroy", "fec_codec_set_encode_path",
-                 "fec_codec_set_copy_path", "fec_codec_set_plan_path", "fec_codec_info", "fec_codec_set_episode_dedup", "fec_debug_stamps", "fec_codec_geometry",
+                 "fec_encode_tile_fetch", "fec_codec_set_copy_path", "fec_codec_set_plan_path", "fec_codec_info", "fec_codec_set_episode_dedup", "fec_debug_stamps", "fec_codec_geometry",
                  "fec_codec_generator", "fec_encode_batch", "fec_decode_batch", "fec_decode_plan",
                  "fec_decode_stream_create", "fec_decode_stream_destroy", "fec_decode_stream_state",
                  "fec_decode_stream_push", "fec_streams_create", "fec_streams_destroy", "fec_streams_encode",

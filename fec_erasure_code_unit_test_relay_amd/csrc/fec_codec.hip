@@ -1155,6 +1155,28 @@ int fec_codec_set_encode_path(fec_codec* c, int path) {
     return FEC_OK;
 }
 
+int fec_encode_tile_fetch(int max_payload, int T, int B, int N, int seg, int* R, int* issued, int* live_body,
+                          int* live_front) {
+    if (max_payload < 0 || T < 0 || B < 0 || N < 0 || N > T) return FEC_ERR_ARG;
+    const int L = max_payload, k = T - N + 1, np = B, n = k + np;
+    const fec::TileGeom tg = fec::tile_geometry(k, np, L, seg != 0);
+    const bool have = (L & 3) == 0 && tg.ok &&
+                      (seg ? fec::fec_encode_tile_seg_kernel_for(k, np, L) : fec::fec_encode_tile_kernel_for(k, np, L));
+    int body = 0, front = 0;
+    if (have) {
+        const int CPR = (L + 15) >> 4;
+        for (int c = 0; c < tg.ngl * 256; ++c) {
+            body += fec::tile_piece_live(tg.R, CPR, n, c, false);
+            front += np > 0 && fec::tile_piece_live(tg.R, CPR, n, c, fec::kTileFrontTrim);
+        }
+    }
+    if (R) *R = have ? tg.R : 0;
+    if (issued) *issued = have ? tg.ngl * 256 : 0;
+    if (live_body) *live_body = body;
+    if (live_front) *live_front = front;
+    return have ? 1 : 0;
+}
+
 int fec_timing_enable(fec_codec* c, int enable) {
     if (!c) return FEC_ERR_ARG;
     c->timing = enable != 0;

@@ -7,8 +7,11 @@
 // Encoder_Basic.cpp:48-74, codingOperations.cpp:131-147).
 //
 // Organisation: a workgroup (4 waves) owns a contiguous run of tiles of R = 4*PPW packets and walks
-// it; only the tile in front of its first one is read twice (the n-1 packets of parity history), so
-// HBM reads are L bytes per packet plus ~1/tiles_per_wg.  Per tile:
+// it; of the tile in front of its first one only the last n-1 rows (the parity history) are read a
+// second time, and a tile's LDS-DMA fetches the tile's own R rows and nothing of the next tile's
+// (tile_piece_live, fec_kernels.h), so HBM reads are L bytes per packet plus (n-1)/(R*tiles_per_wg)
+// plus the 128-byte lines shared by neighbouring slabs: 1.033 x the payload at the headline
+// (309.9 MB for 300.0 MB; 1.161 x while both were fetched whole).  Per tile:
 //   * the tile's payload rows (one contiguous R*L-byte slab) arrive in LDS by LDS-DMA
 //     (buffer_load ... lds), issued two tiles ahead: no registers hold loads in flight, and rows
 //     outside [-history, P) come back as zero (buffer range check) -- the X_{t'<t0} = 0 semantics;
@@ -296,16 +299,25 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
     // 16-byte aligned; the DMA's destination is lane-linear, its per-lane source picks the row
     // piece (tile-invariant offsets, computed once).  A row's last piece also brings the first
     // bytes of the next row (never read as payload: past L they are the zero pad's business).
+    // The instructions cover ngl * 4 KB, more than the tile's R rows: the pieces past them (the
+    // next tile's first rows, which its own DMA fetches) are dead (tile_piece_live) and are issued
+    // out of range like the rows in front of the stream.  Their offset here is 2^31: added (mod
+    // 2^32) to the tile's base it gives either a negative sum, replaced like those rows', or, under
+    // a negative base (>= -16 KB: one tile's rows), one of at least 2^31 - 16 KB, past every
+    // payload buffer (< 2^31 - 64 KB, the launchers' bound).  No instruction more than before.
     const int CPR = (L + 15) >> 4;  // 16-byte pieces per row
     const int RS = CPR * 16;
-    int srel[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    auto piece_rel = [&](int j, bool front) __attribute__((always_inline)) {
         const int c = (j * 4 + (tid >> 6)) * 64 + lane;
         const int row = c / CPR;
-        srel[j] = row * L + (c - row * CPR) * 16;
-    }
-    auto issue = [&](int it) __attribute__((always_inline)) {
+        return tile_piece_live(R, CPR, n, c, front) ? static_cast<uint32_t>(row * L + (c - row * CPR) * 16)
+                                                    : 0x80000000u;
+    };
+    uint32_t srel[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) srel[j] = piece_rel(j, false);
+    // front: the tile in front of the run, of which only the last n-1 rows are fetched
+    auto issue = [&](int it, bool front = false) __attribute__((always_inline)) {
         const int row0 = (first - 1 + it) * R;
         const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
         const uint32_t dst = lds_in + (it & 1) * in_bytes;
@@ -313,11 +325,12 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j < ngl) {
-                const int o = base + srel[j];
+                const int o = static_cast<int>(static_cast<uint32_t>(base) + (front ? piece_rel(j, true) : srel[j]));
+                const uint32_t vo = static_cast<uint32_t>(o < 0 ? 0x7fffffff : o);
                 if (a.nt & 2)
-                    dma16_nt(rs4, static_cast<uint32_t>(o < 0 ? 0x7fffffff : o), dst + (j * 4 + wv) * 1024);
+                    dma16_nt(rs4, vo, dst + (j * 4 + wv) * 1024);
                 else
-                    dma16(rs4, static_cast<uint32_t>(o < 0 ? 0x7fffffff : o), dst + (j * 4 + wv) * 1024);
+                    dma16(rs4, vo, dst + (j * 4 + wv) * 1024);
                 ++vm_issued;
             }
         }
@@ -337,10 +350,14 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
     // nor in front of an instance's first tile (its rows read as zero: the parity rows' zeros)
     // (a.nt bit 2, FEC_VR_HIST0=1: computed anyway, as before)
     const int it0 = (NP == 0 || (SEG && seg_t0 == 0 && !(a.nt & 4))) ? 1 : 0;
-    issue(it0);
+    issue(it0, kTileFrontTrim && it0 == 0);
     if (cnt >= it0 + 1) issue(it0 + 1);
+    // of the tile in front (it == 0) only rows [R-(n-1), R) reach parity rows that are kept: phases
+    // A and B run for the wave slices from sl_front on only (a row below R-(n-1) inside such a slice
+    // is computed from the zeros of its dead pieces; its products land below row R, dropped in C)
+    const int sl_front = kTileFrontTrim ? (R - (n - 1)) / PPW : 0;
 
-    uint32_t H[K];
+    uint32_t H[K] = {};
     for (int it = it0; it <= cnt; ++it) {
         // tile it's input: every VMEM instruction issued after it may still be in flight
         wait_vm(static_cast<int>(vm_issued - vm_mark[it & 1]));
@@ -364,7 +381,7 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
         }
 
         // ---- A: window words and position words of the own item
-        if (active) {
+        if (active && (it > 0 || W >= sl_front)) {
             const int t = row0 + p;
             int lv = L;
             if (has_len) {
@@ -437,7 +454,7 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
 #else
 #pragma unroll 1
 #endif
-                for (int sl = 0; sl < 4; ++sl) {
+                for (int sl = it > 0 ? 0 : sl_front; sl < 4; ++sl) {
                     const int it_item = (sl * PPW + pl) * NS4 + g;
                     const int pp = sl * PPW + pl;
                     const uint32_t* src = pw + it_item * PWS;

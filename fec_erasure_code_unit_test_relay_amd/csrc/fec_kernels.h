@@ -132,6 +132,20 @@ constexpr TileGeom tile_geometry(int k, int np, int L, bool seg = false) {
     return t;
 }
 
+// Which of the 16-byte pieces a tile's LDS-DMA issues (ngl * 256 of them, piece c = row c / CPR,
+// CPR = ceil(L / 16) pieces per row) are fetched: the pieces of the tile's own R rows, and in the
+// tile in front of a workgroup's run (front) only those of its last n-1 rows, the parity history.
+// A dead piece is issued with an out-of-range offset: no memory request, zeros in LDS.  The one
+// definition for the kernel (fec_encode_tile.hip) and the host's count (fec_encode_tile_fetch).
+constexpr bool tile_piece_live(int R, int CPR, int n, int c, bool front) {
+    return c < R * CPR && (!front || c >= (R - (n - 1)) * CPR);
+}
+// Whether the tile in front of a run is trimmed to those rows (else it is fetched like a body tile).
+#ifndef FEC_TILE_FRONT_TRIM
+#define FEC_TILE_FRONT_TRIM 1  // (0: an A/B build, make EXTRA=-DFEC_TILE_FRONT_TRIM=0 OUT=... BUILD=...)
+#endif
+constexpr bool kTileFrontTrim = FEC_TILE_FRONT_TRIM != 0;
+
 // fec_encode_tile_kernel<k, n-k, L> for L = 300 (the reference's payload size, L fixed at compile
 // time) or <k, n-k, 0> (L from the arguments) (fec_encode_tile.hip), else nullptr.  256 threads.
 const void* fec_encode_tile_kernel_for(int k, int np, int L);

@@ -67,6 +67,14 @@ int fec_codec_info(const fec_codec *codec, char *buf, size_t size);
  * wave-sequence kernels, all slower) are retired and return FEC_ERR_ARG.  Every path produces
  * identical bytes; the switch exists for tests and A/B timing. */
 int fec_codec_set_encode_path(fec_codec *codec, int path);
+/* Host-only (no device call): the payload fetch of the tile encoder for (max_payload, T, B, N), one
+ * stream (seg = 0) or the variable-rate schedule's segment mode (seg = 1).  Returns 1 when a tile
+ * kernel exists for the tuple, else 0 (outputs zeroed).  R: packets per tile; issued: 16-byte
+ * LDS-DMA pieces a tile's instructions cover; live_body: those fetched from memory in a tile of a
+ * workgroup's run (R * ceil(max_payload / 16); the others are issued out of range); live_front:
+ * those fetched in the tile in front of a run (the parity history; 0 without parity). */
+int fec_encode_tile_fetch(int max_payload, int T, int B, int N, int seg, int *R, int *issued, int *live_body,
+                          int *live_front);
 /* The same switch for the decoder's received-packet copy kernel: 0 automatic (the LDS-tile
  * specialised kernel when one is compiled for (k, n-k) and max_payload % 4 == 0, else the generic
  * one), 1 generic, 2 LDS-tile specialised.  Ids 3-6 (barrier-free wave, persistent tile, chunk and

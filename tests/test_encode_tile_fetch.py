@@ -1,0 +1,59 @@
+"""The tile encoder's payload fetch as the library itself counts it (fec_encode_tile_fetch, host
+only): a tile's LDS-DMA instructions cover whole 4 KB steps, and only the 16-byte pieces of the
+tile's own rows are fetched from memory; of the tile in front of a workgroup's run only the pieces
+of its last n-1 rows, the parity history (measured and kept: DESIGN.md §7)."""
+import ctypes
+
+import pytest
+
+from fec_erasure_code_unit_test_relay_amd._lib import lib
+
+# tests/test_gpu_parity.py's ENC_CONFIGS and the tuples of config 4's schedule (tests/test_vr.py)
+ENC_CONFIGS = [(10, 3, 3), (10, 5, 2), (10, 1, 1), (10, 0, 0), (10, 2, 2), (10, 5, 5),
+               (10, 7, 7), (10, 9, 9), (10, 10, 10), (10, 8, 4), (10, 5, 4), (10, 9, 8), (10, 4, 1),
+               (4, 6, 2), (12, 4, 2), (10, 9, 1), (10, 10, 1)]
+CONFIG4 = [(10, b, b) for b in (0, 1, 2, 5, 6, 7, 8, 9, 10)]
+FRONT_TRIMMED = True  # the library's default build (FEC_TILE_FRONT_TRIM, fec_kernels.h)
+
+
+def fetch(L, T, B, N, seg):
+    R, issued, body, front = (ctypes.c_int() for _ in range(4))
+    st = lib().fec_encode_tile_fetch(L, T, B, N, seg, ctypes.byref(R), ctypes.byref(issued), ctypes.byref(body),
+                                     ctypes.byref(front))
+    assert st in (0, 1), st
+    return st, R.value, issued.value, body.value, front.value
+
+
+@pytest.mark.parametrize("L", [4, 64, 300])
+@pytest.mark.parametrize("seg,tbn", [(0, t) for t in ENC_CONFIGS] + [(1, t) for t in CONFIG4])
+def test_live_pieces(seg, tbn, L):
+    T, B, N = tbn
+    st, R, issued, body, front = fetch(L, T, B, N, seg)
+    if st == 0:
+        assert (R, issued, body, front) == (0, 0, 0, 0)
+        return
+    n = T - N + 1 + B
+    cpr = -(-L // 16)
+    assert R > 0 and R % 4 == 0 and R >= n - 1
+    assert body == R * cpr
+    assert issued >= body and issued % 256 == 0
+    if B == 0:
+        assert front == 0
+    elif FRONT_TRIMMED:
+        assert front == (n - 1) * cpr
+    else:
+        assert front == body
+
+
+def test_headline_and_segment_tiles():
+    assert fetch(300, 10, 3, 3, 0) == (1, 24, 512, 456, 456 if not FRONT_TRIMMED else 190)
+    # segment mode's tiles of the issue's table: (k, n-k) = (5,6), (11,0), (4,7)
+    for tbn, R, issued in [((10, 6, 6), 16, 512), ((10, 0, 0), 36, 768), ((10, 7, 7), 12, 256)]:
+        st, r, iss, body, _ = fetch(300, *tbn, 1)
+        assert (st, r, iss, body) == (1, R, issued, R * 19)
+
+
+def test_no_tile_kernel():
+    assert fetch(302, 10, 3, 3, 0)[0] == 0    # max_payload % 4 != 0
+    assert fetch(1500, 10, 3, 3, 0)[0] == 0   # the rows do not fit the tile
+    assert lib().fec_encode_tile_fetch(300, 3, 1, 4, 0, None, None, None, None) < 0  # N > T

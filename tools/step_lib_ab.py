@@ -62,6 +62,7 @@ for rnd in range(12):
         torch.cuda.synchronize()
         res[i].append((time.perf_counter() - t0) / 100 * 1e3)
 for i, p in enumerate(sys.argv[1:]):
+    print(f"{os.path.basename(p)}: rounds (ms/step, in order) " + " ".join(f"{v:.4f}" for v in res[i]), flush=True)
     r = sorted(res[i])
     print(f"{os.path.basename(p)}: step median {r[len(r) // 2]:.4f} ms, best {r[0]:.4f} ms", flush=True)
 print("outputs equal" if same else "outputs DIFFER", flush=True)
