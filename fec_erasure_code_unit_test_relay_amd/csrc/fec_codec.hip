@@ -63,10 +63,8 @@ struct fec_codec {
     int encode_path = 0;         // 0 auto, 1 generic, 5 tile (the ids of round 2's paths are kept)
     int cus = 0;                        // compute units of the device
     const void* tile_kernel = nullptr;  // contiguous-chunk LDS-tile encode (fec_encode_tile.hip)
-    int tile_ppw = 0;                   // its packets per wave slice (tile = 4 * tile_ppw packets)
-    int tile_lds = 0, tile_lds_len = 0; // its dynamic LDS per workgroup (without / with lengths)
+    fec::TileGeom tile{};               // its geometry (tile_geometry)
     int tile_per_cu = 0;                // its resident workgroups per CU
-    int tile_off[9] = {};               // off_in, in_bytes, off_pw, off_q, off_out, off_len, ngl, nso, off_scratch
     const void* copy_fast = nullptr;  // specialised decode copy kernel (LDS tiles)
     int copyf_tp = 0;
     int copy_path = 0;           // 0 auto, 1 generic, 2 specialised (LDS tiles)
@@ -194,12 +192,6 @@ int codec_init(fec_codec* c, int max_payload, int T, int B, int N) {
             break;
         }
     if (!c->enc_tp || !c->copy_tp) return FEC_ERR_ARG;
-    // tuning overrides of the specialised kernels' largest tile (power of two, 8..64)
-    auto tile_cap = [](const char* name) {
-        const char* v = std::getenv(name);
-        const int t = v ? std::atoi(v) : 64;
-        return (t >= 8 && t <= 64) ? t : 64;
-    };
     {
         int dev = 0;
         HIP_TRY(hipGetDevice(&dev));
@@ -209,23 +201,10 @@ int codec_init(fec_codec* c, int max_payload, int T, int B, int N) {
         const fec::TileGeom tg = fec::tile_geometry(g.k, g.n - g.k, g.L);
         if (tg.ok) c->tile_kernel = fec::fec_encode_tile_kernel_for(g.k, g.n - g.k, g.L);
         if (c->tile_kernel) {
-            c->tile_lds = tg.lds;
-            c->tile_lds_len = tg.lds_len;
-            c->tile_ppw = tg.PPW;
-            c->tile_off[0] = tg.off_in;
-            c->tile_off[1] = tg.in_bytes;
-            c->tile_off[2] = tg.off_pw;
-            c->tile_off[3] = tg.off_q;
-            c->tile_off[4] = tg.off_out;
-            c->tile_off[5] = tg.off_len;
-            c->tile_off[6] = tg.ngl;
-            c->tile_off[7] = tg.nso;
-            c->tile_off[8] = tg.off_scratch;
-        }
-        if (c->tile_kernel) {
-            HIP_TRY(hipFuncSetAttribute(c->tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, c->tile_lds_len));
+            c->tile = tg;
+            HIP_TRY(hipFuncSetAttribute(c->tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tg.lds_len));
             int per_cu = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->tile_kernel, 256, c->tile_lds));
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, c->tile_kernel, 256, tg.lds));
             c->tile_per_cu = per_cu;
             if (per_cu <= 0) c->tile_kernel = nullptr;
         }
@@ -236,35 +215,13 @@ int codec_init(fec_codec* c, int max_payload, int T, int B, int N) {
     // (23 KB LDS) take 135 us per 1M packets against 148 us at 64 and 154 us at 16
     // (profiles/r01/decode_diag/copy_tile_ab.txt, same-process A/B).
     if (c->copy_fast)
-        for (int tp = tile_cap("FEC_COPY_TILE"); tp >= 8; tp >>= 1)
+        for (int tp = 64; tp >= 8; tp >>= 1)
             if (c->copyf_lds(tp) <= (tp == 8 ? kLdsBudget : kCopyLdsBudget)) {
                 c->copyf_tp = tp;
                 break;
             }
     if (!c->copyf_tp) c->copy_fast = nullptr;
-    // experiments (FEC_SIDE_CUS / FEC_SIDE_PRIO): the planner's side stream on a CU subset, or at
-    // the lowest / highest stream priority
-    const char* side_cus = std::getenv("FEC_SIDE_CUS");
-    const char* side_prio = std::getenv("FEC_SIDE_PRIO");
-    if (side_cus && std::atoi(side_cus) > 0) {
-        int dev = 0, cus = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        const int want = std::min(cus, std::atoi(side_cus));
-        std::vector<uint32_t> mask((cus + 31) / 32, 0u);
-        for (int i = 0; i < want; ++i) {
-            const int cu = static_cast<int>(static_cast<int64_t>(i) * cus / want);
-            mask[cu / 32] |= 1u << (cu % 32);
-        }
-        HIP_TRY(hipExtStreamCreateWithCUMask(&c->side, static_cast<uint32_t>(mask.size()), mask.data()));
-    } else if (side_prio) {
-        int least = 0, greatest = 0;
-        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIP_TRY(hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking,
-                                            std::strcmp(side_prio, "high") == 0 ? greatest : least));
-    } else {
-        HIP_TRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
-    }
+    HIP_TRY(hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     return FEC_OK;
@@ -322,7 +279,7 @@ int launch_encode_tile(fec_codec* c, const uint8_t* d_payload, const int32_t* d_
                        int64_t P, uint8_t* d_cw, int32_t* d_cwlen, hipStream_t s) {
     const Geometry& g = c->g;
     history = std::min<int64_t>(std::max<int64_t>(0, history), g.n - 1);
-    const int R = 4 * c->tile_ppw;
+    const int R = c->tile.R;
     // 32-bit buffer offsets: batches beyond 2 GB go in chunks of whole tiles (each chunk sees the
     // n-1 rows in front of it as history; the chunk start stays 16-byte aligned in the output)
     const int64_t max_rows = ((int64_t(0x7fffffff) - 65536) / std::max(g.L, g.CW) - g.n) / R * R;
@@ -348,48 +305,25 @@ int launch_encode_tile(fec_codec* c, const uint8_t* d_payload, const int32_t* d_
     a.cw_len = d_cwlen;
     a.ptab = c->d_ptab;
     a.L = g.L;
-    a.CW = g.CW;
-    a.NS4 = c->ns4();
-    a.PPW = c->tile_ppw;
-    a.rem = g.S - 4 * (a.NS4 - 1);
-    a.nvl = g.L / 4 - g.k * (a.NS4 - 1);
+    a.g = c->tile;
     const int64_t ntiles = (P + R - 1) / R;
     // one wave of resident workgroups, each a contiguous run of tiles (plus the tile in front)
-    int64_t slots = static_cast<int64_t>(std::max(1, c->cus)) * c->tile_per_cu;
-    if (const char* v = std::getenv("FEC_TILE_WPC"))
-        slots = static_cast<int64_t>(std::max(1, c->cus)) * std::max(1, std::min(c->tile_per_cu, std::atoi(v)));
+    const int64_t slots = static_cast<int64_t>(std::max(1, c->cus)) * c->tile_per_cu;
     const int64_t tpw = (ntiles + slots - 1) / slots;
     a.tiles_per_wg = static_cast<int>(tpw);
     a.ntiles = static_cast<int>(ntiles);
-    a.off_in = c->tile_off[0];
-    a.in_bytes = c->tile_off[1];
-    a.off_pw = c->tile_off[2];
-    a.off_q = c->tile_off[3];
-    a.off_out = c->tile_off[4];
-    a.off_len = c->tile_off[5];
-    a.ngl = c->tile_off[6];
-    a.nso = c->tile_off[7];
-    a.off_scratch = c->tile_off[8];
-    a.dbg = 0;
-#ifdef FEC_ABLATION_BUILD
-    // timing ablations (work skipped, codewords wrong by design): only in a diagnostic build,
-    // `make EXTRA=-DFEC_ABLATION_BUILD OUT=... BUILD=...`; the product library ignores FEC_TILE_DBG
-    if (const char* v = std::getenv("FEC_TILE_DBG")) a.dbg = std::atoi(v);
-#endif
     a.seg = nullptr;
     a.cur_rows = a.old_rows = nullptr;
     a.cur_len = a.old_len = nullptr;
     a.W = 0;
-    // bit 0: non-temporal codeword stores, bit 1: non-temporal payload loads.  Default 2: the
-    // payload rows are read once; 0.2983 - 0.3015 vs 0.3058 - 0.3088 ms per step, encoder 141 - 143
-    // vs 145 us (three alternations in one process, profiles/r05/headline/r05zz_tile_nt_ab.txt);
-    // non-temporal codeword stores (bit 0) slow the encoder to 170 - 177 us (the copy reads them next)
+    // non-temporal payload loads (bit 1): the payload rows are read once; 0.2983 - 0.3015 vs
+    // 0.3058 - 0.3088 ms per step with plain loads, encoder 141 - 143 vs 145 us (three alternations
+    // in one process, profiles/r05/headline/r05zz_tile_nt_ab.txt).  The codeword stores stay temporal.
     a.nt = 2;
-    if (const char* v = std::getenv("FEC_TILE_NT")) a.nt = std::atoi(v) & 3;
     const int64_t blocks = (ntiles + tpw - 1) / tpw;
     void* args[] = {&a};
     return c->launch(FEC_KERNEL_ENCODE, c->tile_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), args,
-                     d_len ? c->tile_lds_len : c->tile_lds, s);
+                     d_len ? c->tile.lds_len : c->tile.lds, s);
 }
 
 int launch_encode(fec_codec* c, const uint8_t* d_payload, const int32_t* d_len, int64_t history,
@@ -485,12 +419,11 @@ int launch_plan(fec_codec* c, const uint8_t* d_er, int64_t P, void* d_ws, size_t
     ea.keys = w.keys;
     ea.reps_tr = w.reps_tr;
     ea.stamps = (c->stamp_kernel == FEC_KERNEL_DEC_SCAN) ? c->d_stamps : nullptr;
-    // a wave per 1024 packets (fec_shapes.hip), at most FEC_EPISODE_GRID waves (A/B switch)
-    // one wave per CU: beside the headline copy, 977 waves at 1 M packets took its CUs (0.3224 vs
-    // 0.3066 ms per step with 245; 384: 0.3000 - 0.3015 vs 0.2987 - 0.2992, profiles/r06/r06u, r06w)
-    int64_t egrid = 256;
-    if (const char* v = std::getenv("FEC_EPISODE_GRID")) egrid = std::max(1, std::atoi(v));
-    const int64_t sblocks = std::min<int64_t>((P + 1023) / 1024, egrid);
+    // a wave per 1024 packets (fec_shapes.hip), at most kEpisodeGrid waves, one per CU: beside the
+    // headline copy, 977 waves at 1 M packets took its CUs (0.3224 vs 0.3066 ms per step with 245;
+    // 384: 0.3000 - 0.3015 vs 0.2987 - 0.2992, profiles/r06/r06u, r06w)
+    constexpr int64_t kEpisodeGrid = 256;
+    const int64_t sblocks = std::min<int64_t>((P + 1023) / 1024, kEpisodeGrid);
     hipLaunchKernelGGL(fec::fec_episode_kernel, dim3(static_cast<unsigned>(sblocks)), dim3(64), 0, s, ea);
     HIP_TRY(hipGetLastError());
     if (int st = c->end(stop, s)) return st;
@@ -522,31 +455,28 @@ int launch_plan(fec_codec* c, const uint8_t* d_er, int64_t P, void* d_ws, size_t
     // The work lists live on the device: (episode, diagonal) replays of one episode per shape
     // (41 x 11 at (10,3,3) on bin/erasure.bin) and one item per duplicate episode.  Graph-replayed
     // plan beside the copy: 8192 / 512 workgroups 175 / 169 us (tools/graph_parts.py).
-    int pgrid = 1024;
-    if (const char* v = std::getenv("FEC_PLAN_GRID")) pgrid = std::max(1, std::atoi(v));
+    constexpr int kPlanGrid = 1024;
     if (fast_ok && c->plan_path != 1) {
         pa.rules = c->d_rules_log;
         void* args[] = {&pa};
-        HIP_TRY(hipLaunchKernel(c->plan_fast, dim3(pgrid), dim3(64), args, 0, s));
+        HIP_TRY(hipLaunchKernel(c->plan_fast, dim3(kPlanGrid), dim3(64), args, 0, s));
     } else {
         const int plan_lds = 768 + g.n * g.n + 2 * g.k * g.n + 32 * 16 + 32 * 32 + g.k * (1 + g.n);
-        hipLaunchKernelGGL(fec::fec_plan_kernel, dim3(pgrid), dim3(64), plan_lds, s, pa);
+        hipLaunchKernelGGL(fec::fec_plan_kernel, dim3(kPlanGrid), dim3(64), plan_lds, s, pa);
     }
     HIP_TRY(hipGetLastError());
     return c->end(stop, s);
 }
 
-// The two-tiles-per-workgroup copy for this codec, or null: the one test launch_copy and
-// fec_codec_info both use (nt = the copy's non-temporal loads, which the paired kernel needs).
-const void* copy_pair_kernel(const fec_codec* c, bool nt) {
-    const char* pv = std::getenv("FEC_COPY_PAIR");
-    if ((pv && pv[0] == '0') || !nt || !c->copy_fast) return nullptr;
-    if (16 + c->copyf_tp * c->g.CW + 16 > 6 * 16 * 256) return nullptr;  // the stage of one tile in registers
+// The two-tiles-per-workgroup copy for this codec, or null (the stage of one tile must fit the
+// kernel's registers): the one test launch_copy and fec_codec_info both use.
+const void* copy_pair_kernel(const fec_codec* c) {
+    if (!c->copy_fast || 16 + c->copyf_tp * c->g.CW + 16 > fec::kPairQ * 16 * 256) return nullptr;
     return fec::fec_copy_pair_kernel_for(c->g.k, c->g.n - c->g.k);
 }
 
 int launch_copy(fec_codec* c, const uint8_t* d_cw, const uint8_t* d_er, int64_t P, uint8_t* d_out,
-                int32_t* d_outlen, hipStream_t s, bool skip_erased = false) {
+                int32_t* d_outlen, hipStream_t s) {
     const Geometry& g = c->g;
     const int64_t Pout = P - g.T;
     if (Pout <= 0) return FEC_OK;
@@ -569,11 +499,6 @@ int launch_copy(fec_codec* c, const uint8_t* d_cw, const uint8_t* d_er, int64_t 
         fa.raw_bytes = c->copyf_raw(fa.TP);
         fa.out_bytes = round16(fa.TP * g.L);
         fa.stamps = (c->stamp_kernel == FEC_KERNEL_DEC_COPY) ? c->d_stamps : nullptr;
-        fa.skip_erased = skip_erased ? 1 : 0;
-        // non-temporal codeword loads and payload stores: 0.318 vs 0.338 ms per bench step
-        // (tools/step_ab.py, same process, profiles/r02/decode_diag/copy_nt_ab.txt)
-        fa.nt = 1;
-        if (const char* v = std::getenv("FEC_COPY_NT")) fa.nt = std::atoi(v) ? 1 : 0;
         // (Tried: 32 bytes of LDS padding after every 16 tile rows, which gives the 32 lanes of a
         // ds_read_b32 group distinct banks -- conflict cycles 3.81 M -> 31 k per launch -- but the
         // padded staging made the step 2.2 % slower in the same process, 0.3228 vs 0.3157 ms:
@@ -582,8 +507,8 @@ int launch_copy(fec_codec* c, const uint8_t* d_cw, const uint8_t* d_er, int64_t 
         // two tiles per workgroup, the second one's loads in flight while the first is converted
         // (copy_pair_kernel: when the stage of one tile fits the registers): 0.3055 vs 0.3126 ms per
         // step, copy 143.6 vs 151.5 us in the step (profiles/r05/headline/r05zu_copy_pair_ab.txt);
-        // FEC_COPY_PAIR=0: one tile per workgroup
-        const void* pk = copy_pair_kernel(c, fa.nt != 0);
+        // one tile per workgroup (fec_copy_fast_kernel) only where the stage does not fit
+        const void* pk = copy_pair_kernel(c);
         const int64_t tiles = (Pout + fa.TP - 1) / fa.TP;
         const int64_t blocks = pk ? (tiles + 1) / 2 : tiles;
         // 256 threads (one per (packet, group) item of the tile rounded up to waves, 320 at (10,3,3),
@@ -618,8 +543,7 @@ int launch_copy(fec_codec* c, const uint8_t* d_cw, const uint8_t* d_er, int64_t 
 }
 
 // Recovered packets -> rec_list (fec_compact_kernel), on `s` after the plan.
-int launch_compact(fec_codec* c, int64_t P, uint8_t* d_out, int32_t* d_outlen, void* d_ws, size_t ws_bytes,
-                   hipStream_t s, int64_t row_off = 0, bool zero_lost = false) {
+int launch_compact(fec_codec* c, int64_t P, void* d_ws, size_t ws_bytes, hipStream_t s) {
     const Geometry& g = c->g;
     if (P - g.T <= 0) return FEC_OK;
     if (int st = check_ws(c, P, d_ws, ws_bytes)) return st;
@@ -631,13 +555,6 @@ int launch_compact(fec_codec* c, int64_t P, uint8_t* d_out, int32_t* d_outlen, v
     ca.sym_ok = w.sym_ok;
     ca.k = g.k;
     ca.rec_list = w.rec_list;
-    // the copy writes every row (zero rows and length 0 for erased packets); recovered rows are
-    // overwritten by the recovery, which runs after it
-    ca.zero_lost = zero_lost ? 1 : 0;
-    ca.out = d_out;
-    ca.out_len = d_outlen;
-    ca.L = g.L;
-    ca.row_off = row_off;
     if (!c->compact_fresh)  // a second compaction of one plan starts over
         HIP_TRY(hipMemsetAsync(w.counters + 2, 0, 4, s));
     c->compact_fresh = false;
@@ -655,7 +572,7 @@ int launch_recover(fec_codec* c, const uint8_t* d_cw, int64_t P, uint8_t* d_out,
     if (Pout <= 0) return FEC_OK;
     if (int st = check_ws(c, P, d_ws, ws_bytes)) return st;
     if (!compacted)
-        if (int st = launch_compact(c, P, d_out, d_outlen, d_ws, ws_bytes, s, row_off)) return st;
+        if (int st = launch_compact(c, P, d_ws, ws_bytes, s)) return st;
     const Ws w = ws_carve(g, P, d_ws);
     fec::RecArgs ra;
     ra.cw = d_cw;
@@ -680,7 +597,6 @@ int launch_recover(fec_codec* c, const uint8_t* d_cw, int64_t P, uint8_t* d_out,
     // (fec_recover_kernel_t's kRecStageChunks)
     const int span = (g.k + g.n - 1) * g.CW + 32;
     ra.stage_bytes = (span <= 12 * 1024 && g.n <= 17) ? ((span + 15) & ~15) : 0;
-    if (const char* v = std::getenv("FEC_REC_STAGE")) ra.stage_bytes = std::atoi(v) ? ra.stage_bytes : 0;
     // a wave per recovered packet: up to 4096 waves
     const unsigned rgrid = static_cast<unsigned>(std::min<int64_t>((Pout + 3) / 4, 1024));
     const int maxn = g.n <= 17 ? 17 : 32;
@@ -697,18 +613,12 @@ int launch_recover(fec_codec* c, const uint8_t* d_cw, int64_t P, uint8_t* d_out,
 
 // Full decode on `s`: the erasure-only plan runs on the codec's side stream concurrently with the
 // systematic copy, joined before the recovery pass (fork/join through events, capturable).
-// FEC_RECOVER_BESIDE=1 (A/B switch, off by default): the recovery on the side stream behind the
-// planner chain, beside a copy that leaves the erased rows alone (the compaction zeroes the lost
-// ones).  Slower wherever it was measured: the headline step 0.3157 - 0.3163 vs 0.3103 - 0.3114 ms,
-// config 3 (360 000 packets, whose 56 us copy is shorter than the ~100 us chain) 0.1253 vs 0.1235 ms
-// per decode (profiles/r06/r06v, r06w; round 3: profiles/r03/r03y_recover_beside_ab.txt).
-bool recover_beside(const fec_codec* c, const uint8_t* d_out) {
-    // only the specialised copies leave erased rows alone (fec_copy_fast.hip, skip_erased)
-    if (!c->copy_fast || c->copy_path == 1 || (reinterpret_cast<uintptr_t>(d_out) & 3) != 0) return false;
-    const char* v = std::getenv("FEC_RECOVER_BESIDE");
-    return v && v[0] == '1';
-}
-
+// (Removed: the recovery on the side stream behind the planner chain, beside a copy that left the
+// erased rows alone.  Slower wherever it was measured: the headline step 0.3157 - 0.3163 vs
+// 0.3103 - 0.3114 ms, config 3 (360 000 packets, whose 56 us copy is shorter than the ~100 us
+// chain) 0.1253 vs 0.1235 ms per decode (profiles/r06/r06v_recover_beside_step_ab.txt,
+// r06w_recover_beside_config3_ab.txt); round 3: 0.3198 vs 0.3162 ms
+// (profiles/r03/r03y_recover_beside_ab.txt).)
 int launch_decode(fec_codec* c, const uint8_t* d_cw, const uint8_t* d_er, int64_t P, uint8_t* d_out,
                   int32_t* d_outlen, void* d_ws, size_t ws_bytes, hipStream_t s) {
     if (P - c->g.T <= 0) return FEC_OK;
@@ -716,20 +626,11 @@ int launch_decode(fec_codec* c, const uint8_t* d_cw, const uint8_t* d_er, int64_
     HIP_TRY(hipEventRecord(c->ev_fork, s));
     HIP_TRY(hipStreamWaitEvent(c->side, c->ev_fork, 0));
     if (int st = launch_plan(c, d_er, P, d_ws, ws_bytes, c->side)) return st;
-    if (recover_beside(c, d_out)) {
-        if (int st = launch_compact(c, P, d_out, d_outlen, d_ws, ws_bytes, c->side, 0, true)) return st;
-        if (int st = launch_recover(c, d_cw, P, d_out, d_outlen, d_ws, ws_bytes, c->side, 0, true)) return st;
-        HIP_TRY(hipEventRecord(c->ev_join, c->side));
-        if (int st = launch_copy(c, d_cw, d_er, P, d_out, d_outlen, s, true)) return st;
-        HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
-        return FEC_OK;
-    }
-    if (int st = launch_compact(c, P, d_out, d_outlen, d_ws, ws_bytes, c->side)) return st;
+    if (int st = launch_compact(c, P, d_ws, ws_bytes, c->side)) return st;
     HIP_TRY(hipEventRecord(c->ev_join, c->side));
     // The copy writes every row (erased ones as zero rows, length 0); the recovery overwrites the
-    // recovered ones after the join.  Rounds 2 and 3 measured the alternatives slower in the step
-    // (a copy that leaves erased rows to a recovery running beside it: 0.3198 vs 0.3162 ms,
-    // profiles/r03/r03y_recover_beside_ab.txt; the plan beside the encoder; profiles/r02/decode_diag).
+    // recovered ones after the join.  (The plan beside the encoder measured slower in the step too,
+    // profiles/r02/decode_diag.)
     if (int st = launch_copy(c, d_cw, d_er, P, d_out, d_outlen, s)) return st;
     HIP_TRY(hipStreamWaitEvent(s, c->ev_join, 0));
     return launch_recover(c, d_cw, P, d_out, d_outlen, d_ws, ws_bytes, s, 0, true);
@@ -778,7 +679,7 @@ int launch_decode_stream(fec_codec* c, fec_decode_stream* st, const uint8_t* d_c
     HIP_TRY(hipEventRecord(c->ev_fork, s));
     HIP_TRY(hipStreamWaitEvent(c->side, c->ev_fork, 0));
     if (int e = launch_plan(c, er_c, Pp, d_ws, ws_bytes, c->side)) return e;
-    if (int e = launch_compact(c, Pp, d_out, d_outlen, d_ws, ws_bytes, c->side, next_out - cut)) return e;
+    if (int e = launch_compact(c, Pp, d_ws, ws_bytes, c->side)) return e;
     HIP_TRY(hipEventRecord(c->ev_join, c->side));
     // received rows [next_out, end - T): a copy over packets [next_out, end)
     const int64_t Pc = end - next_out;
@@ -1094,9 +995,7 @@ int fec_codec_info(const fec_codec* c, char* buf, size_t size) {
     else
         std::snprintf(enc, sizeof(enc), "fec_encode_kernel");
     char cpy[64];
-    const char* ntv = std::getenv("FEC_COPY_NT");
-    const bool pair = copy_pair_kernel(c, !(ntv && !std::atoi(ntv))) != nullptr;
-    if (c->copy_fast && c->copy_path != 1 && pair)
+    if (c->copy_path != 1 && copy_pair_kernel(c))
         std::snprintf(cpy, sizeof(cpy), "fec_copy_pair_kernel<%d, %d>", c->g.k, np);
     else if (c->copy_fast && c->copy_path != 1)
         std::snprintf(cpy, sizeof(cpy), "fec_copy_fast_kernel<%d, %d>", c->g.k, np);
@@ -1106,7 +1005,7 @@ int fec_codec_info(const fec_codec* c, char* buf, size_t size) {
                   "{\"k\": %d, \"n\": %d, \"S\": %d, \"CW\": %d, \"encode_kernel\": \"%s\", "
                   "\"copy_kernel\": \"%s\", \"encode_tile_packets\": %d, \"encode_tile_workgroups_per_cu\": %d, "
                   "\"copy_tile\": %d, \"plan_specialised\": %d}",
-                  c->g.k, c->g.n, c->g.S, c->g.CW, enc, cpy, 4 * c->tile_ppw, c->tile_per_cu, c->copyf_tp,
+                  c->g.k, c->g.n, c->g.S, c->g.CW, enc, cpy, c->tile.R, c->tile_per_cu, c->copyf_tp,
                   c->plan_fast ? 1 : 0);
     return FEC_OK;
 }
@@ -1167,7 +1066,7 @@ int fec_encode_tile_fetch(int max_payload, int T, int B, int N, int seg, int* R,
         const int CPR = (L + 15) >> 4;
         for (int c = 0; c < tg.ngl * 256; ++c) {
             body += fec::tile_piece_live(tg.R, CPR, n, c, false);
-            front += np > 0 && fec::tile_piece_live(tg.R, CPR, n, c, fec::kTileFrontTrim);
+            front += np > 0 && fec::tile_piece_live(tg.R, CPR, n, c, true);
         }
     }
     if (R) *R = have ? tg.R : 0;
@@ -1265,13 +1164,7 @@ constexpr int64_t kServerIdleTicks = 5000000;  // 50 ms of the 100 MHz counter w
 // holds a launch of those behind it (a plain stream shares one of GPU_MAX_HW_QUEUES queues with the
 // others: a 50 ms server held a launch on another stream for 49.9 ms; on a high-priority stream the
 // worst of 13 launches, the null stream's included, took 18-23 us, profiles/r05/r05q_queue_prio.txt).
-// FEC_CODER_PLAIN_STREAMS=1 (diagnostic) creates them plainly.
 hipError_t coder_stream_create(hipStream_t* s) {
-    static const bool plain = [] {
-        const char* v = std::getenv("FEC_CODER_PLAIN_STREAMS");
-        return v && v[0] == '1';
-    }();
-    if (plain) return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
     int least = 0, greatest = 0;
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) greatest = 0;
     return hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest);

@@ -37,16 +37,12 @@
 #include "fec_kernels.h"
 #include "fec_vr_cf.h"
 
-#include <cstdlib>
 #include <utility>
 
 namespace fec {
 namespace {
 
 constexpr int kTileThreads = 256;
-#ifndef FEC_TILE_MINWG
-#define FEC_TILE_MINWG 5  // workgroups per CU the register budget is sized for
-#endif
 
 template <typename F, int... Is>
 __device__ __forceinline__ void tfor_impl(F&& f, std::integer_sequence<int, Is...>) {
@@ -207,8 +203,8 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
 
     const int lane = threadIdx.x & 63;
     const int tid = threadIdx.x;
-    const int L = CL ? LC : a.L, CW = CL ? CG.CW : a.CW, NS4 = CL ? CG.NS4 : a.NS4;
-    const int PPW = CL ? CG.PPW : a.PPW, R = 4 * PPW;
+    const int L = CL ? LC : a.L, CW = CL ? CG.CW : a.g.CW, NS4 = CL ? CG.NS4 : a.g.NS4;
+    const int PPW = CL ? CG.PPW : a.g.PPW, R = 4 * PPW;
     // Segment mode (a.seg, the variable-rate schedule): this workgroup encodes tiles [t0, t0+cnt)
     // of one encoder instance -- a fresh encoder over the payload rows [sfirst, sfirst+P) -- and
     // writes row t to the frames' array of its role (cur before the role switch, old after) in the
@@ -232,12 +228,11 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
     const int pay_bytes = segm ? P * (CL ? LC : a.L) : a.payload_bytes;
     const int32_t* len_base = segm ? (a.len_base ? a.len_base + sfirst : nullptr) : a.len_base;
     const int len_bytes = segm ? 4 * P : a.len_bytes;
-    const int dbg = CL ? 0 : a.dbg;  // timing experiments: the runtime-L kernel only
-    const int nvl = CL ? CG.nvl : a.nvl, rem = CL ? CG.rem : a.rem;
-    const int off_in = CL ? CG.off_in : a.off_in, in_bytes = CL ? CG.in_bytes : a.in_bytes;
-    const int off_pw = CL ? CG.off_pw : a.off_pw, off_q = CL ? CG.off_q : a.off_q;
-    const int off_out = CL ? CG.off_out : a.off_out, off_len = CL ? CG.off_len : a.off_len;
-    const int off_scratch = CL ? CG.off_scratch : a.off_scratch;
+    const int nvl = CL ? CG.nvl : a.g.nvl, rem = CL ? CG.rem : a.g.rem;
+    const int off_in = CL ? CG.off_in : a.g.off_in, in_bytes = CL ? CG.in_bytes : a.g.in_bytes;
+    const int off_pw = CL ? CG.off_pw : a.g.off_pw, off_q = CL ? CG.off_q : a.g.off_q;
+    const int off_out = CL ? CG.off_out : a.g.off_out, off_len = CL ? CG.off_len : a.g.off_len;
+    const int off_scratch = CL ? CG.off_scratch : a.g.off_scratch;
     const int last_g = NS4 - 1;
     const int ipw = PPW * NS4;                 // items per wave slice
     const bool active = lane < ipw;
@@ -276,8 +271,8 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
 
     const int first = segm ? seg_t0 : static_cast<int>(blockIdx.x) * a.tiles_per_wg;
     const int cnt = segm ? seg_cnt : min(a.tiles_per_wg, a.ntiles - first);  // real tiles of this workgroup (>= 1)
-    const int ngl = CL ? CG.ngl : a.ngl;                     // payload LDS-DMA instructions per wave per tile
-    const int nso = CL ? CG.nso : a.nso;                     // 16-byte stores per thread per tile
+    const int ngl = CL ? CG.ngl : a.g.ngl;                   // payload LDS-DMA instructions per wave per tile
+    const int nso = CL ? CG.nso : a.g.nso;                   // 16-byte stores per thread per tile
     // segment mode's row-chunk iterations (two stores each: the cur and old resources)
     const int nch_seg = (CW + 15) >> 4;
     const int nit_seg = (R * nch_seg + kTileThreads - 1) / kTileThreads;
@@ -350,12 +345,12 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
     // nor in front of an instance's first tile (its rows read as zero: the parity rows' zeros)
     // (a.nt bit 2, FEC_VR_HIST0=1: computed anyway, as before)
     const int it0 = (NP == 0 || (SEG && seg_t0 == 0 && !(a.nt & 4))) ? 1 : 0;
-    issue(it0, kTileFrontTrim && it0 == 0);
+    issue(it0, it0 == 0);
     if (cnt >= it0 + 1) issue(it0 + 1);
     // of the tile in front (it == 0) only rows [R-(n-1), R) reach parity rows that are kept: phases
     // A and B run for the wave slices from sl_front on only (a row below R-(n-1) inside such a slice
     // is computed from the zeros of its dead pieces; its products land below row R, dropped in C)
-    const int sl_front = kTileFrontTrim ? (R - (n - 1)) / PPW : 0;
+    const int sl_front = (R - (n - 1)) / PPW;
 
     uint32_t H[K] = {};
     for (int it = it0; it <= cnt; ++it) {
@@ -448,12 +443,8 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
 
         // ---- B: this wave's products over every item of the tile, XORed into the parity rows
         if constexpr (NPW > 0) {
-            if (active && !(dbg & 1)) {
-#ifdef FEC_TILE_BUNROLL
-#pragma unroll
-#else
+            if (active) {
 #pragma unroll 1
-#endif
                 for (int sl = it > 0 ? 0 : sl_front; sl < 4; ++sl) {
                     const int it_item = (sl * PPW + pl) * NS4 + g;
                     const int pp = sl * PPW + pl;
@@ -532,14 +523,12 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
             // dwords written: n, except the last group of a packet: up to the packet end (the dword
             // shared with the next packet is that packet's first lane's)
             const int cntw = !emit ? 0 : (t >= P ? 1 : (is_last ? ((p + 1) * CW >> 2) - d0 : n));
-            if (!(dbg & 2)) {
-                uint32_t* outw = reinterpret_cast<uint32_t*>(out) + d0;
-                uint32_t* zdst = scratch + tid;
+            uint32_t* outw = reinterpret_cast<uint32_t*>(out) + d0;
+            uint32_t* zdst = scratch + tid;
 #pragma unroll
-                for (int qq = 0; qq < n; ++qq) {
-                    const uint32_t lo = qq == 0 ? prev : X[qq - 1];
-                    *(qq < cntw ? outw + qq : zdst) = __builtin_amdgcn_perm(X[qq], lo, shsel);
-                }
+            for (int qq = 0; qq < n; ++qq) {
+                const uint32_t lo = qq == 0 ? prev : X[qq - 1];
+                *(qq < cntw ? outw + qq : zdst) = __builtin_amdgcn_perm(X[qq], lo, shsel);
             }
             }
         }
@@ -615,11 +604,12 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
                 const bool full = inb && c + 16 <= lim;
                 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
                 const v4u vv = {v.x, v.y, v.z, v.w};
-                const int so = full && !(dbg & 4) ? gbase + c : 0x7ffffff0;
-                if (a.nt & 1)
-                    __builtin_amdgcn_raw_buffer_store_b128(vv, rc, so, 0, 2);  // nt
-                else
-                    __builtin_amdgcn_raw_buffer_store_b128(vv, rc, so, 0, 0);
+                // temporal stores: the copy reads the codewords next (non-temporal ones slowed the
+                // encoder to 170 - 177 us, profiles/r05/headline/r05zz_tile_nt_ab.txt).  Without the
+                // former store-policy branch the (9,5) L = 300 instance takes 150 VGPRs for 149, at
+                // the same 3 workgroups per CU; holding it at 149 (this loop not unrolled) cost the
+                // headline encoder 2.5 us (profiles/codecpaths/README.txt)
+                __builtin_amdgcn_raw_buffer_store_b128(vv, rc, full ? gbase + c : 0x7ffffff0, 0, 0);
                 ++vm_issued;
             }
             // trimmed wire size of packet tid (FEC_Encoder.cpp:55-60): 1 + last non-zero byte; a
@@ -659,9 +649,10 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
 
 // Workgroups per CU the register budget is sized for: five (96 VGPRs), or four / three when a
 // wave's share of the K*NP coefficient tables would not fit beside the rest (it spilled to scratch).
+constexpr int kTileMinWg = 5;
 template <int K, int NP>
 constexpr int tile_min_wg() {
-    return K * NP > 36 ? 3 : (K * NP >= 27 ? 4 : FEC_TILE_MINWG);
+    return K * NP > 36 ? 3 : (K * NP >= 27 ? 4 : kTileMinWg);
 }
 
 template <int K, int NP, int LC, bool SEG>
@@ -675,11 +666,6 @@ __global__ __launch_bounds__(kTileThreads, (tile_min_wg<K, NP>())) void fec_enco
     }
 }
 
-#ifdef FEC_WAVE_ONLY
-#define FEC_ENC_TILE_LIST(X) X(8, 3)
-#define FEC_ENC_TILE_L300_LIST(X) X(8, 3)
-#define FEC_ENC_TILE_SEG300_LIST(X) X(8, 3)
-#else
 #define FEC_ENC_TILE_LIST(X) \
     X(8, 3) X(9, 5) X(11, 0) X(10, 1) X(9, 2) X(7, 4) X(6, 5) X(5, 6) X(4, 7) X(3, 8) X(2, 9)  \
     X(10, 3) X(9, 3) X(10, 4) X(8, 4) X(10, 5) X(7, 5) X(3, 9)
@@ -689,7 +675,6 @@ __global__ __launch_bounds__(kTileThreads, (tile_min_wg<K, NP>())) void fec_enco
 #define FEC_ENC_TILE_SEG300_LIST(X) \
     X(8, 3) X(9, 5) X(11, 0) X(10, 1) X(9, 2) X(7, 4) X(6, 5) X(5, 6) X(4, 7) X(10, 3) X(9, 3) X(10, 4) \
     X(8, 4) X(10, 5) X(7, 5) X(10, 0) X(9, 1) X(6, 0) X(9, 0) X(8, 2) X(8, 1) X(5, 0)
-#endif
 
 #define FEC_ENC_TILE_INST(K, NP) \
     template __global__ void fec_encode_tile_kernel<K, NP, 0, false>(EncTileArgs); \
@@ -701,7 +686,7 @@ FEC_ENC_TILE_L300_LIST(FEC_ENC_TILE_INST300)
 FEC_ENC_TILE_SEG300_LIST(FEC_ENC_TILE_SEG_INST300)
 
 const void* fec_encode_tile_kernel_for(int k, int np, int L) {
-    if (!std::getenv("FEC_TILE_RUNTIME_L") && L == 300) {
+    if (L == 300) {
 #define FEC_ENC_TILE_CASE300(K, NP) \
     if (k == K && np == NP) return reinterpret_cast<const void*>(&fec_encode_tile_kernel<K, NP, 300, false>);
         FEC_ENC_TILE_L300_LIST(FEC_ENC_TILE_CASE300)

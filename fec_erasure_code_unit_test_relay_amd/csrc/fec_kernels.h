@@ -42,50 +42,18 @@ struct EncArgs {
     int xin_bytes, xout_bytes;  // 16-aligned LDS carve sizes
 };
 
-struct EncTileArgs {
-    const uint8_t* payload_base;  // row -history (4-byte aligned, L % 4 == 0)
-    const int32_t* len_base;      // lengths of rows -history.. (null: all L)
-    int payload_bytes;            // (history + P) * L < 2^31 (the launcher splits larger batches)
-    int len_bytes;                // (history + P) * 4
-    int history;                  // valid rows before row 0 (<= n-1)
-    int P;
-    uint8_t* cw;                  // 16-byte aligned
-    int cw_bytes;                 // P * CW < 2^31
-    int32_t* cw_len;
-    const uint32_t* ptab;         // [k][n-k][8] register tables of G's parity coefficients
-    int L, CW, NS4;
-    int PPW;                      // packets per wave slice (tile R = 4 * PPW packets, PPW*CW % 4 == 0)
-    int rem;                      // sub-streams in the last group (1..4)
-    int nvl;                      // payload dwords of a row from dword K*(NS4-1) on (last group)
-    int tiles_per_wg, ntiles;     // consecutive tiles per workgroup; ceil(P / R)
-    int ngl;                      // 1 KB LDS-DMA pieces per wave per tile (4 * ngl KB >= R*L + 4K + 8)
-    int nso;                      // 16-byte output stores per thread per tile (ceil(R*CW / 4096))
-    int off_in, in_bytes, off_pw, off_q, off_out, off_len;  // dynamic LDS carve-up (bytes)
-    int off_scratch;              // 1 KB: a dword per thread for writes that must land nowhere
-    int dbg;                      // timing experiments only (FEC_TILE_DBG): 1 no parity products,
-                                  // 2 no codeword words, 4 no output stores
-    int nt;                       // 1: codeword stores non-temporal (FEC_TILE_NT); 2: payload loads non-temporal;
-                                  // 4: segment mode computes the zero history tile of an instance start
-    // segment mode (variable-rate schedule, fec_vr.cpp): null for one stream.  Per workgroup 6
-    // int64: first seq of the encoder instance (its row 0), its role-switch seq, its rows P,
-    // t0 | cnt << 32 (tiles [t0, t0+cnt) of the instance), and the byte offsets of the instance's
-    // first cur row and first old row in cur_rows / old_rows (the compact layout, fec_vr.h).
-    // history = 0; rows before / from the role switch go to cur_rows / old_rows at stride W (the
-    // instance's CW rounded to 16).
-    const int64_t* seg;
-    uint8_t* cur_rows;
-    uint8_t* old_rows;
-    int32_t* cur_len;
-    int32_t* old_len;
-    int64_t W;
-};
-
 // Geometry of the tile encoder for (k, n-k, L): one definition for the host launcher and the
 // kernels specialised on L at compile time.  ok = 0: the tile form does not apply.
 struct TileGeom {
     int ok;
-    int S, CW, NS4, PPW, R, rem, nvl, ngl, nso;
-    int off_in, in_bytes, off_pw, off_q, off_out, off_len, off_scratch;
+    int S, CW, NS4;
+    int PPW, R;        // packets per wave slice; tile R = 4 * PPW packets (PPW*CW % 4 == 0)
+    int rem;           // sub-streams in the last group (1..4)
+    int nvl;           // payload dwords of a row from dword K*(NS4-1) on (last group)
+    int ngl;           // 1 KB LDS-DMA pieces per wave per tile (4 * ngl KB >= R*L + 4K + 8)
+    int nso;           // 16-byte output stores per thread per tile (ceil(R*CW / 4096))
+    int off_in, in_bytes, off_pw, off_q, off_out, off_len;  // dynamic LDS carve-up (bytes)
+    int off_scratch;   // 1 KB: a dword per thread for writes that must land nowhere
     int lds, lds_len;  // dynamic LDS without / with the length rows
 };
 // seg: the segment-mode layout, whose output tile holds rows at the compact layout's stride W
@@ -132,6 +100,36 @@ constexpr TileGeom tile_geometry(int k, int np, int L, bool seg = false) {
     return t;
 }
 
+struct EncTileArgs {
+    const uint8_t* payload_base;  // row -history (4-byte aligned, L % 4 == 0)
+    const int32_t* len_base;      // lengths of rows -history.. (null: all L)
+    int payload_bytes;            // (history + P) * L < 2^31 (the launcher splits larger batches)
+    int len_bytes;                // (history + P) * 4
+    int history;                  // valid rows before row 0 (<= n-1)
+    int P;
+    uint8_t* cw;                  // 16-byte aligned
+    int cw_bytes;                 // P * CW < 2^31
+    int32_t* cw_len;
+    const uint32_t* ptab;         // [k][n-k][8] register tables of G's parity coefficients
+    int L;
+    TileGeom g;                   // tile_geometry(k, n-k, L); the kernels specialised on L use their own
+    int tiles_per_wg, ntiles;     // consecutive tiles per workgroup; ceil(P / R)
+    int nt;                       // 2: payload loads non-temporal; 4: segment mode computes the zero
+                                  // history tile of an instance start
+    // segment mode (variable-rate schedule, fec_vr.cpp): null for one stream.  Per workgroup 6
+    // int64: first seq of the encoder instance (its row 0), its role-switch seq, its rows P,
+    // t0 | cnt << 32 (tiles [t0, t0+cnt) of the instance), and the byte offsets of the instance's
+    // first cur row and first old row in cur_rows / old_rows (the compact layout, fec_vr.h).
+    // history = 0; rows before / from the role switch go to cur_rows / old_rows at stride W (the
+    // instance's CW rounded to 16).
+    const int64_t* seg;
+    uint8_t* cur_rows;
+    uint8_t* old_rows;
+    int32_t* cur_len;
+    int32_t* old_len;
+    int64_t W;
+};
+
 // Which of the 16-byte pieces a tile's LDS-DMA issues (ngl * 256 of them, piece c = row c / CPR,
 // CPR = ceil(L / 16) pieces per row) are fetched: the pieces of the tile's own R rows, and in the
 // tile in front of a workgroup's run (front) only those of its last n-1 rows, the parity history.
@@ -140,11 +138,6 @@ constexpr TileGeom tile_geometry(int k, int np, int L, bool seg = false) {
 constexpr bool tile_piece_live(int R, int CPR, int n, int c, bool front) {
     return c < R * CPR && (!front || c >= (R - (n - 1)) * CPR);
 }
-// Whether the tile in front of a run is trimmed to those rows (else it is fetched like a body tile).
-#ifndef FEC_TILE_FRONT_TRIM
-#define FEC_TILE_FRONT_TRIM 1  // (0: an A/B build, make EXTRA=-DFEC_TILE_FRONT_TRIM=0 OUT=... BUILD=...)
-#endif
-constexpr bool kTileFrontTrim = FEC_TILE_FRONT_TRIM != 0;
 
 // fec_encode_tile_kernel<k, n-k, L> for L = 300 (the reference's payload size, L fixed at compile
 // time) or <k, n-k, 0> (L from the arguments) (fec_encode_tile.hip), else nullptr.  256 threads.
@@ -190,12 +183,11 @@ struct CopyFastArgs {
     int raw_bytes;              // codeword tile + slack (16-aligned)
     int out_bytes;              // payload tile (16-aligned)
     uint64_t* stamps;           // diagnostics: per-workgroup phase timestamps (null = off)
-    int skip_erased;            // 1: leave erased packets' rows and lengths to fec_recover_kernel
-    int nt;                     // 1: non-temporal codeword loads and payload stores
 };
 
 // fec_copy_fast_kernel<k, n-k> for the instantiated pairs (fec_copy_fast.hip), else nullptr.
 const void* fec_copy_fast_kernel_for(int k, int np);
+constexpr int kPairQ = 6;  // 16-byte chunks per thread a tile's stage may take (6 * 16 * 256 = 24 KB)
 // Two consecutive tiles per workgroup, the second one's loads in flight while the first is
 // converted (same arguments and LDS as fec_copy_fast_kernel; stage <= kPairQ * 4 KB), or nullptr.
 const void* fec_copy_pair_kernel_for(int k, int np);
@@ -272,11 +264,6 @@ struct CompactArgs {
     const uint8_t* sym_ok;         // [P][k] from the planner
     int k;
     int32_t* rec_list;             // (x, x + src_d[x]) pairs
-    int zero_lost;                 // 1: lost packets' rows (zeros) and lengths (0) written here
-    uint8_t* out;
-    int32_t* out_len;
-    int L;
-    int64_t row_off;               // packet x goes to output row x - row_off (x < row_off: skipped)
 };
 __global__ void fec_compact_kernel(CompactArgs a);
 

@@ -439,7 +439,7 @@ __global__ __launch_bounds__(64) void fec_plan_kernel(PlanArgs a) {
 // ------------------------------------------------------------------------------------------
 // Erased output packets whose k symbols are all recovered (their plan rows -- or their shape
 // representative's -- say so, Decoder_Basic.cpp:76-79) -> rec_list as (x, x + src_d[x]) pairs,
-// counted in counters[2]; the others are lost (zero_lost: their rows and lengths zeroed here).
+// counted in counters[2]; the others are lost (the copy wrote their rows and lengths as zeros).
 // Lane (j, i) = symbol i of entry j, J = 64 / k entries per wave and round, one append atomic
 // per wave and round.
 __global__ __launch_bounds__(256) void fec_compact_kernel(CompactArgs a) {
@@ -473,17 +473,6 @@ __global__ __launch_bounds__(256) void fec_compact_kernel(CompactArgs a) {
                 const int at = base + __builtin_popcountll(okm & ((1ull << lane) - 1ull));
                 a.rec_list[2 * at] = x;
                 a.rec_list[2 * at + 1] = xr;
-            }
-        }
-        if (a.zero_lost) {
-            uint64_t lost = __builtin_amdgcn_ballot_w64(lead && !ok);
-            while (lost) {
-                const int l0 = __builtin_ctzll(lost);
-                lost &= lost - 1;
-                const int xl = __builtin_amdgcn_readlane(x, l0);
-                if (xl < a.row_off) continue;
-                for (int b = lane; b < a.L; b += 64) a.out[static_cast<int64_t>(xl - a.row_off) * a.L + b] = 0;
-                if (lane == 0) a.out_len[xl - a.row_off] = 0;
             }
         }
     }

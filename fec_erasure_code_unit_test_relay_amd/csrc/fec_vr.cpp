@@ -1708,23 +1708,9 @@ int launch_tile_tuple(const fec_vr_plan* v, const fec_vr_plan::TileTuple& tt, co
     a.cw_len = nullptr;
     a.ptab = v->d_gtab + tt.toff;
     a.L = v->plan.L;
-    a.CW = tg.CW;
-    a.NS4 = tg.NS4;
-    a.PPW = tg.PPW;
-    a.rem = tg.rem;
-    a.nvl = tg.nvl;
+    a.g = tg;
     a.tiles_per_wg = 0;
     a.ntiles = 0;
-    a.ngl = tg.ngl;
-    a.nso = tg.nso;
-    a.off_in = tg.off_in;
-    a.in_bytes = tg.in_bytes;
-    a.off_pw = tg.off_pw;
-    a.off_q = tg.off_q;
-    a.off_out = tg.off_out;
-    a.off_len = tg.off_len;
-    a.off_scratch = tg.off_scratch;
-    a.dbg = 0;
     a.nt = 0;
     a.seg = v->d_seg + 6 * tt.seg0;
     a.cur_rows = d_cw_cur;

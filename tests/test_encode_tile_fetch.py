@@ -13,7 +13,7 @@ ENC_CONFIGS = [(10, 3, 3), (10, 5, 2), (10, 1, 1), (10, 0, 0), (10, 2, 2), (10, 
                (10, 7, 7), (10, 9, 9), (10, 10, 10), (10, 8, 4), (10, 5, 4), (10, 9, 8), (10, 4, 1),
                (4, 6, 2), (12, 4, 2), (10, 9, 1), (10, 10, 1)]
 CONFIG4 = [(10, b, b) for b in (0, 1, 2, 5, 6, 7, 8, 9, 10)]
-FRONT_TRIMMED = True  # the library's default build (FEC_TILE_FRONT_TRIM, fec_kernels.h)
+FRONT_TRIMMED = True  # the front tile is always trimmed (tile_piece_live, fec_kernels.h)
 
 
 def fetch(L, T, B, N, seg):

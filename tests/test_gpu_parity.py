@@ -241,6 +241,47 @@ def test_copy_fast_variable_lengths_and_sizes():
             assert (out.cpu().numpy() == np.stack(want)).all(), (Lx, tbn, cpath)
 
 
+def test_copy_kernels_tile_edges():
+    """Both specialised copy kernels (two tiles per workgroup at (10,3,3); one tile at (10,10,10),
+    whose stage is over 24 KB) at output counts around their tile: a lone tile, a pair with an
+    empty, a partial and a full second tile, an odd tile count.  Variable lengths, erased codewords
+    replaced by garbage; the oracle's per-packet coders give the expected rows (its decoder is
+    causal: the first Pout outputs of the long stream are those of the stream cut after Pout + T)."""
+    Lx = 300
+    for tbn, kernel in [((10, 3, 3), "fec_copy_pair_kernel"), ((10, 10, 10), "fec_copy_fast_kernel")]:
+        T, B, N = tbn
+        c = fec.Codec(Lx, T, B, N)
+        info = c.info()
+        assert info["copy_kernel"].startswith(kernel), (tbn, info)
+        TP = info["copy_tile"]
+        Pmax = 3 * TP
+        rng = np.random.default_rng(300 + B)
+        pat = (rng.random(Pmax + T) < 0.05).astype(np.uint8)  # (drawn first: the same for any tile size)
+        assert pat[:Pmax].any()  # erased rows among the outputs
+        lens = rng.integers(0, Lx + 1, size=Pmax + T).astype(np.int32)
+        lens[::9] = Lx
+        enc = oracle.Encoder(Lx, T, B, N)
+        dec = oracle.Decoder(Lx, T, B, N)
+        src = oracle.fill_payload(0, Pmax + T, Lx, 5)
+        cws, want_len, want = [], [], []
+        for t in range(Pmax + T):
+            cw, size = enc.onTransmit(src[t], int(lens[t]), t)
+            cws.append(rng.integers(0, 256, size=cw.size, dtype=np.uint8) if pat[t] else cw)
+            out, p = dec.onReceive(None if pat[t] else cw, size, t, bool(pat[t]))
+            if t >= T:
+                want.append(out)
+                want_len.append(p)
+        cws, want, want_len = np.stack(cws), np.stack(want), np.array(want_len)
+        for Pout in sorted({1, TP - 1, TP, TP + 1, 2 * TP, 2 * TP + 1, 3 * TP}):
+            cw_dev = torch.from_numpy(cws[:Pout + T]).cuda()
+            er_dev = torch.from_numpy(pat[:Pout + T]).cuda()
+            for cpath in ("fast", "generic"):
+                c.set_copy_path(cpath)
+                out, ln = c.decode(cw_dev, er_dev)
+                assert (ln.cpu().numpy() == want_len[:Pout]).all(), (tbn, Pout, cpath)
+                assert (out.cpu().numpy() == want[:Pout]).all(), (tbn, Pout, cpath)
+
+
 def test_decode_startup_and_dense_erasures():
     P = 600
     pat = np.zeros(P + 10, dtype=np.uint8)

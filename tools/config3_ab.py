@@ -1,6 +1,7 @@
 """In-process A/B of BASELINE config 3's decode (device-resident, (10,5,2), 360 000 packets of
-bin/erasure.bin) over environment switches the library reads per launch, alternating variants:
-    python tools/config3_ab.py FEC_PLAN_GRID=1024 FEC_PLAN_GRID=4096,FEC_X=1 [rounds]"""
+bin/erasure.bin) over environment switches the library reads per launch (one under trial in a
+working tree), alternating variants:
+    python tools/config3_ab.py FEC_X=1024 FEC_X=4096,FEC_Y=1 [rounds]"""
 import os
 import statistics
 import sys

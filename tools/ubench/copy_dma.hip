@@ -227,8 +227,6 @@ int main() {
     a.NS4 = NS4;
     a.T = static_cast<int>(T);
     a.stamps = nullptr;
-    a.skip_erased = 0;
-    a.nt = 1;
     hipEvent_t e0, e1;
     CHECK(hipEventCreate(&e0));
     CHECK(hipEventCreate(&e1));
