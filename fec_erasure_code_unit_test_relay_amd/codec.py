@@ -362,6 +362,53 @@ class StreamGroup:
                                        _stream_handle(torch)), "fec_streams_decode")
         return out, out_len
 
+    def _burst_args(self, ids, counts):
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        assert ids.ndim == 1 and counts.shape == ids.shape
+        # a count < 1 is the library's to refuse; it adds no rows here
+        return ids, counts, int(np.maximum(counts, 0).sum(dtype=np.int64))
+
+    def encode_burst(self, ids, counts, payload, lengths=None, out=None, out_len=None):
+        """ids, counts: host int32 [M], counts[m] >= 1 consecutive packets of stream ids[m]; payload
+        [R, L] uint8 GPU with R = sum(counts), stream ids[m]'s rows from row sum(counts[:m]) on
+        -> (cw [R, CW], sizes [R]), equal to counts[m] encode() calls per stream."""
+        import torch
+        ids, counts, R = self._burst_args(ids, counts)
+        assert payload.dtype == torch.uint8 and payload.is_cuda and payload.is_contiguous()
+        assert tuple(payload.shape) == (R, self.L)
+        if lengths is not None:
+            assert lengths.dtype == torch.int32 and lengths.is_cuda and lengths.numel() == R
+        out, out_len = _check_out(torch, out, out_len, R, self.CW, payload.device)
+        check(lib().fec_streams_encode_burst(self._h, ids.ctypes.data_as(ctypes.c_void_p),
+                                             counts.ctypes.data_as(ctypes.c_void_p), ids.size, _ptr(payload),
+                                             _ptr(lengths), _ptr(out), _ptr(out_len), _stream_handle(torch)),
+              "fec_streams_encode_burst")
+        return out, out_len
+
+    def decode_burst(self, ids, counts, erasure, codewords, out=None, out_len=None):
+        """ids, counts: host int32 [M]; erasure: host uint8 [R]; codewords [R, CW] GPU (rows as in
+        encode_burst) -> (payload [R, L], lengths [R]): a row = packet seq-T of its stream, equal
+        to counts[m] decode() calls per stream."""
+        import torch
+        ids, counts, R = self._burst_args(ids, counts)
+        er = np.ascontiguousarray(erasure, dtype=np.uint8)
+        assert er.size == R
+        assert codewords.dtype == torch.uint8 and codewords.is_cuda and codewords.is_contiguous()
+        assert tuple(codewords.shape) == (R, self.CW)
+        out, out_len = _check_out(torch, out, out_len, R, self.L, codewords.device)
+        check(lib().fec_streams_decode_burst(self._h, ids.ctypes.data_as(ctypes.c_void_p),
+                                             counts.ctypes.data_as(ctypes.c_void_p), ids.size,
+                                             er.ctypes.data_as(ctypes.c_void_p), _ptr(codewords), _ptr(out),
+                                             _ptr(out_len), _stream_handle(torch)), "fec_streams_decode_burst")
+        return out, out_len
+
+    def state(self, stream_id: int):
+        """(packets sent, packets received) of one stream."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        check(lib().fec_streams_state(self._h, stream_id, ctypes.byref(a), ctypes.byref(b)), "fec_streams_state")
+        return a.value, b.value
+
 
 class FEC_Encoder:
     """FEC_Encoder(max_payload, T, B, N) -- per-packet interface (src/FEC_Encoder.cpp:22-68)."""
@@ -437,4 +484,17 @@ def plan_host(max_payload: int, T: int, B: int, N: int, erasure: np.ndarray) -> 
     fate = np.zeros(e.size, dtype=np.uint8)
     check(lib().fec_plan_host(max_payload, T, B, N, e.ctypes.data_as(ctypes.c_void_p), e.size,
                               fate.ctypes.data_as(ctypes.c_void_p)), "fec_plan_host")
+    return fate[: max(0, e.size - T)]
+
+
+def plan_burst_host(max_payload: int, T: int, B: int, N: int, erasure: np.ndarray, counts) -> np.ndarray:
+    """plan_host through the stream group's burst planner, the stream fed in bursts of `counts`
+    packets (their sum = erasure.size)."""
+    e = np.ascontiguousarray(erasure, dtype=np.uint8)
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    assert int(c.sum(dtype=np.int64)) == e.size
+    fate = np.zeros(e.size, dtype=np.uint8)
+    check(lib().fec_streams_plan_burst_host(max_payload, T, B, N, e.ctypes.data_as(ctypes.c_void_p),
+                                            c.ctypes.data_as(ctypes.c_void_p), c.size,
+                                            fate.ctypes.data_as(ctypes.c_void_p)), "fec_streams_plan_burst_host")
     return fate[: max(0, e.size - T)]

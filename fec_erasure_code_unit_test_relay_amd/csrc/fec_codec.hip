@@ -1710,6 +1710,7 @@ int fec::codec_view(const fec_codec* c, fec::CodecView* v) {
     v->rules = c->d_rules;
     v->wbase_n = c->rules->w_base[g.n];
     v->ES = c->rules->entry_bytes;
+    v->ptab = c->d_ptab;
     return FEC_OK;
 }
 

@@ -313,6 +313,7 @@ struct CodecView {
     const uint8_t* rules;       // decode rule table, raw coefficients (device)
     int64_t wbase_n;            // byte offset of window n's rules
     int ES;                     // rule entry bytes
+    const uint32_t* ptab;       // [k][n-k][8] gf_mul4x tables of G's parity coefficients (device)
 };
 __global__ void fec_block_decode_kernel(BlockArgs a);
 

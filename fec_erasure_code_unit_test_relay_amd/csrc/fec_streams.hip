@@ -13,6 +13,9 @@
 // its byte work: the encoder's closed form (Encoder.cpp:65-98 -> codingOperations.cpp:131-147)
 // over the stream's window, or the decoder's output for packet seq - T (fast path copy,
 // Decoder.cpp:77-108, or the planner's recovery coefficients, codingOperations.cpp:149-232).
+// A burst call (fec_streams_encode_burst / fec_streams_decode_burst) hands over several consecutive
+// packets of each stream and equals that many one-packet calls; its kernels work on chunks of a
+// burst and touch the per-stream state only at the burst's two ends (see "bursts" below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,6 +37,7 @@
 #include <sched.h>
 
 #include "fec_amd.h"
+#include "fec_device.h"
 #include "fec_host.h"
 #include "fec_kernels.h"
 #include "fec_status.h"
@@ -313,6 +317,396 @@ __device__ __forceinline__ void stream_output(const StreamsDecArgs& a, const Str
     if (lane == 0) a.out_len[m] = ln;
 }
 
+// ---- bursts: counts[m] consecutive packets of each stream per call ---------------------------
+// A burst is cut into chunks of at most TP packets, one workgroup each.  A chunk takes the packets
+// in front of it that it needs (the encoder's n-1 windows, the decoder's T+k-1 codewords) from the
+// call's own rows; only a burst's first chunk has packets from before the call in front of it, and
+// reads them from the stream's ring.  The same workgroup, after a barrier, writes the ring with the
+// burst's last packets (from the call's rows): no other workgroup of the launch touches that
+// stream's ring, which takes TP >= n-1 (T+k-1) whenever a burst has more than one chunk.
+
+struct FastDiv {  // x / d by one multiply, exact while x * d < 2^32
+    uint32_t m, d;
+};
+inline FastDiv fast_div(int d) {
+    return FastDiv{d > 1 ? static_cast<uint32_t>(((1ull << 32) + d - 1) / d) : 0u, static_cast<uint32_t>(d)};
+}
+__device__ __forceinline__ int fdiv(FastDiv f, int x) {
+    return f.d == 1 ? x : static_cast<int>(__umulhi(static_cast<uint32_t>(x), f.m));
+}
+
+struct BurstUnit {   // one chunk = one workgroup
+    int64_t row0;    // its first row in the call's row arrays
+    int64_t seq0;    // that row's sequence number in its stream
+    int32_t id;
+    int32_t cnt;     // rows of the chunk (<= TP)
+    int32_t lead;    // rows of the burst in front of the chunk (0: the first chunk)
+    int32_t total;   // rows of the burst
+    int32_t coef0;   // decode: index of the chunk's first coefficient block (its recovered rows, in row order)
+    int32_t pad;
+};
+constexpr uint8_t kRowClamp = 4, kRowErased = 8;  // decode row flags: fate | clamp | erased
+
+struct BurstEncArgs {
+    const uint8_t* payload;  // R rows of L bytes
+    const int32_t* len;      // R payload sizes (null: all L)
+    const BurstUnit* units;
+    uint8_t* win;            // [streams][W][SK] window ring
+    uint8_t* cw;             // R rows of CW bytes
+    int32_t* cw_len;
+    const uint32_t* ptab;    // [k][n-k][8] gf_mul4x tables
+    int L, k, n, S, SP, NS4, CW, SK, SKS, W, TP, ROWS;
+    int off_planes, off_io, off_ring, off_len;  // dynamic LDS carve-up (bytes, multiples of 16)
+    FastDiv dk, dns4, dnq;
+};
+
+struct BurstDecArgs {
+    const uint8_t* cw_in;    // R rows of CW bytes (rows of erased packets are not read)
+    const BurstUnit* units;
+    const uint8_t* flags;    // R bytes: fate | kRowClamp | kRowErased
+    const uint8_t* coefs;    // the recovered rows' k x n blocks
+    uint8_t* ring;           // [streams][kRR][CW]
+    const uint8_t* gf;
+    uint8_t* out;            // R rows of L bytes
+    int32_t* out_len;
+    int L, k, n, CW, CWS, CWD, LW, T, TP, HR, ROWS;
+    int off_rows, off_out, off_coef, off_meta;  // dynamic LDS carve-up
+    FastDiv dk, dlw, dcwd;
+};
+
+// Global bytes g[0, nb) into LDS, byte j at smem[off + (g & 3) + j] (off a multiple of 4): whole
+// dwords with dword loads, the up to 3 + 3 bytes in front of and behind them with byte loads.
+__device__ __forceinline__ void burst_stage(uint8_t* smem, int off, const uint8_t* g, int nb, int t, int nt) {
+    const int a = static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
+    const int head = min(nb, (4 - a) & 3);
+    const int nd = (nb - head) >> 2;
+    const uint32_t* gd = reinterpret_cast<const uint32_t*>(g + head);
+    uint32_t* ld = reinterpret_cast<uint32_t*>(smem + off + ((a + head) & ~3));
+    if (((a + head) & 3) == 0) {
+#pragma unroll 4
+        for (int w = t; w < nd; w += nt) ld[w] = gd[w];
+    }
+    const int tail0 = head + 4 * nd;
+    if (t < head) smem[off + a + t] = g[t];
+    if (t < nb - tail0) smem[off + a + tail0 + t] = g[tail0 + t];
+}
+
+// LDS bytes smem[off, off + nb) to global g[0, nb): whole dwords with dword stores.
+__device__ __forceinline__ void burst_flush(uint8_t* g, const uint8_t* smem, int off, int nb, int t, int nt) {
+    const int a = static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
+    const int head = min(nb, (4 - a) & 3);
+    const int nd = (nb - head) >> 2;
+    const int tail0 = head + 4 * nd;
+    if (nd > 0) {  // then g + head is a dword address
+        uint32_t* gd = reinterpret_cast<uint32_t*>(g + head);
+        const uint8_t* s = smem + off + head;
+        if (((off + head) & 3) == 0) {
+            for (int w = t; w < nd; w += nt) gd[w] = reinterpret_cast<const uint32_t*>(s)[w];
+        } else {
+            for (int w = t; w < nd; w += nt)
+                gd[w] = uint32_t(s[4 * w]) | (uint32_t(s[4 * w + 1]) << 8) | (uint32_t(s[4 * w + 2]) << 16) |
+                        (uint32_t(s[4 * w + 3]) << 24);
+        }
+    }
+    if (t < head) g[t] = smem[off + t];
+    if (t < nb - tail0) g[tail0 + t] = smem[off + tail0 + t];
+}
+
+// One workgroup per chunk.  LDS: the parity tables; the windows of the chunk's packets and of the
+// n-1 in front of them as position planes [i][row][sub-stream] (the four sub-streams of one
+// gf_mul4x sit in one dword); the chunk's payload rows, later its codewords; the ring's rows.
+__global__ __launch_bounds__(256) void fec_streams_encode_burst_kernel(BurstEncArgs a) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    const int tid = threadIdx.x;
+    const BurstUnit u = a.units[blockIdx.x];
+    const int L = a.L, k = a.k, n = a.n, S = a.S, SP = a.SP, NS4 = a.NS4, CW = a.CW, SK = a.SK, SKS = a.SKS;
+    const int W = a.W, ROWS = a.ROWS, np = n - k, H = n - 1;
+    uint32_t* tab = reinterpret_cast<uint32_t*>(smem);
+    uint8_t* planes = smem + a.off_planes;
+    int* lens = reinterpret_cast<int*>(smem + a.off_len);  // per row: payload size; -1 no packet; -2 ring row
+    for (int i = tid; i < k * np * 8; i += 256) tab[i] = a.ptab[i];
+    const int hb = min(H, u.lead);  // rows in front of the chunk that lie in the burst
+    const uint8_t* ringb = a.win + static_cast<int64_t>(u.id) * W * SK;
+    // row r = packet seq0 + r - H
+    for (int r = tid; r < ROWS; r += 256) {
+        const int p = r - H;
+        int v = -1;
+        if (p < u.cnt) {
+            if (p >= -hb)
+                v = a.len ? min(max(a.len[u.row0 + p], 0), L) : L;
+            else if (u.seq0 + p >= 0)
+                v = -2;
+        }
+        lens[r] = v;
+    }
+    const uint8_t* g0 = a.payload + (u.row0 - hb) * L;
+    burst_stage(smem, a.off_io, g0, (hb + u.cnt) * L, tid, 256);
+    for (int r = 0; r < H - hb; ++r) {  // ring rows (first chunk only)
+        const int64_t seq = u.seq0 + r - H;
+        if (seq >= 0) burst_stage(smem, a.off_ring + r * SKS, ringb + (seq % W) * SK, SK, tid, 256);
+    }
+    __syncthreads();
+    // payload byte b of row r at smem[rawoff + r * L + b]
+    const int rawoff = a.off_io + static_cast<int>(reinterpret_cast<uintptr_t>(g0) & 3) - (H - hb) * L;
+    const int nq = (SK + 3) >> 2;
+    const FastDiv dnq = a.dnq;
+    // the dword at any LDS byte offset: two aligned reads
+    auto lds_word = [&](int off) -> uint32_t {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(smem + (off & ~3));
+        return __builtin_amdgcn_alignbyte(w[1], w[0], off & 3);
+    };
+    for (int idx = tid; idx < ROWS * nq; idx += 256) {  // window bytes 4q .. 4q+3 of row r
+        const int r = fdiv(dnq, idx), q = idx - r * nq;
+        const int ln = lens[r];
+        uint32_t w = 0;  // [len_hi, len_lo, payload, zero pad] (Encoder.cpp:75-83)
+        if (ln >= 0) {
+            w = lds_word(rawoff + r * L + 4 * q - 2) & keep_bytes(ln + 2 - 4 * q);
+            if (q == 0) w = (w & 0xffff0000u) | static_cast<uint32_t>(ln >> 8) | (static_cast<uint32_t>(ln & 0xff) << 8);
+        } else if (ln == -2) {
+            const uint8_t* g = ringb + ((u.seq0 + r - H) % W) * SK;
+            w = lds_word(a.off_ring + r * SKS + static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3) + 4 * q);
+        }
+        int s = fdiv(a.dk, 4 * q), i = 4 * q - s * k;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * q + e < SK) planes[(i * ROWS + r) * SP + s] = static_cast<uint8_t>(w >> (8 * e));
+            if (++i == k) i = 0, ++s;
+        }
+    }
+    __syncthreads();  // the planes are complete; the payload rows give way to the codewords
+    uint8_t* gcw = a.cw + u.row0 * CW;
+    const int ao = a.off_io + static_cast<int>(reinterpret_cast<uintptr_t>(gcw) & 3);
+    uint8_t* out = smem + ao;
+    for (int idx = tid; idx < u.cnt * nq; idx += 256) {  // systematic bytes
+        const int p = fdiv(dnq, idx), q = idx - p * nq;
+        int s = fdiv(a.dk, 4 * q), i = 4 * q - s * k;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * q + e < SK) out[p * CW + s * n + i] = planes[(i * ROWS + p + H) * SP + s];
+            if (++i == k) i = 0, ++s;
+        }
+    }
+    // parity column j of four sub-streams: XOR_i G[i][j] * X_{t-(j-i)}[s][i]; rows without a packet are zero
+    for (int jj = 0; jj < np; ++jj) {
+        const int j = k + jj;
+        for (int it = tid; it < u.cnt * NS4; it += 256) {
+            const int p = fdiv(a.dns4, it), g = it - p * NS4;
+            uint32_t acc = 0;
+            for (int i = 0; i < k; ++i) {
+                const uint32_t* t = tab + (i * np + jj) * 8;
+                if (!t[5]) continue;
+                const int r = p + H - (j - i);
+                acc ^= gf_mul4x(t, *reinterpret_cast<const uint32_t*>(planes + (i * ROWS + r) * SP + 4 * g));
+            }
+            uint8_t* o = out + p * CW + 4 * g * n + j;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * g + e < S) o[e * n] = static_cast<uint8_t>(acc >> (8 * e));
+        }
+    }
+    __syncthreads();
+    if (tid < u.cnt) a.cw_len[u.row0 + tid] = last_nonzero_end(out + tid * CW, CW);  // FEC_Encoder.cpp:55-60
+    burst_flush(gcw, smem, ao, u.cnt * CW, tid, 256);
+    if (u.lead != 0) return;
+    // the burst's last min(total, W) windows into the ring
+    const int m = min(u.total, W), t0 = u.total - m;
+    const bool far = u.total > u.cnt;  // they lie (partly) behind this chunk: their payload rows again
+    const uint8_t* g1 = a.payload + (u.row0 + t0) * L;
+    const int raw1 = a.off_io + static_cast<int>(reinterpret_cast<uintptr_t>(g1) & 3);
+    if (far) {
+        __syncthreads();
+        burst_stage(smem, a.off_io, g1, m * L, tid, 256);
+        __syncthreads();
+    }
+    for (int idx = tid; idx < m * nq; idx += 256) {
+        const int tt = fdiv(dnq, idx), q = idx - tt * nq, t = t0 + tt;
+        const int ln = far ? (a.len ? min(max(a.len[u.row0 + t], 0), L) : L) : 0;
+        uint8_t v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int b = min(4 * q + e, SK - 1);
+            if (far) {
+                v[e] = b == 0 ? static_cast<uint8_t>(ln >> 8)
+                              : b == 1 ? static_cast<uint8_t>(ln & 0xff) : (b - 2 < ln ? smem[raw1 + tt * L + b - 2] : 0);
+            } else {
+                const int s = fdiv(a.dk, b), i = b - s * k;
+                v[e] = planes[(i * ROWS + t + H) * SP + s];
+            }
+        }
+        uint8_t* dst = a.win + (static_cast<int64_t>(u.id) * W + (u.seq0 + t) % W) * SK + 4 * q;
+        if ((SK & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(dst) = uint32_t(v[0]) | (uint32_t(v[1]) << 8) | (uint32_t(v[2]) << 16) |
+                                                (uint32_t(v[3]) << 24);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * q + e < SK) dst[e] = v[e];
+        }
+    }
+}
+
+// One workgroup per chunk.  LDS: the GF tables; the codewords of the chunk's packets and of the
+// T+k-1 in front of them (each row at its own dword phase); the recovered rows' coefficient
+// blocks; the chunk's output rows.
+__global__ __launch_bounds__(256) void fec_streams_decode_burst_kernel(BurstDecArgs a) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    const int tid = threadIdx.x;
+    const BurstUnit u = a.units[blockIdx.x];
+    const int L = a.L, k = a.k, n = a.n, CW = a.CW, CWS = a.CWS, CWD = a.CWD, LW = a.LW, T = a.T;
+    const int HR = a.HR, ROWS = a.ROWS, TP = a.TP, kn = k * n;
+    uint8_t* gexp = smem;
+    uint8_t* glog = smem + 512;
+    int* rowoff = reinterpret_cast<int*>(smem + a.off_meta);  // [ROWS] LDS offset of the row's byte 0; -1: none
+    int* cord = rowoff + ROWS;                                // [TP] coefficient block of a recovered row
+    int* lnS = cord + TP;                                     // [TP] output length
+    int* cpS = lnS + TP;                                      // [TP] payload bytes copied
+    uint8_t* fl = reinterpret_cast<uint8_t*>(cpS + TP);       // [TP] row flags
+    for (int i = tid; i < 768; i += 256) smem[i] = a.gf[i];
+    const int hb = min(HR, u.lead);
+    uint8_t* ringb = a.ring + static_cast<int64_t>(u.id) * kRR * CW;
+    // row r = packet seq0 + r - HR; its codeword's address (null: missing, or before the stream)
+    for (int r = tid; r < ROWS; r += 256) {
+        const int p = r - HR;
+        const uint8_t* g = nullptr;
+        if (p < u.cnt) {
+            if (p >= -hb) {
+                const uint8_t f = a.flags[u.row0 + p];
+                if (p >= 0) fl[p] = f;
+                if (!(f & kRowErased)) g = a.cw_in + (u.row0 + p) * CW;
+            } else if (u.seq0 + p >= 0) {
+                g = ringb + ((u.seq0 + p) % kRR) * CW;
+            }
+        }
+        rowoff[r] = g ? a.off_rows + r * CWS + static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3) : -1;
+    }
+    __syncthreads();
+    auto row_src = [&](int r) -> const uint8_t* {
+        if (rowoff[r] < 0) return nullptr;
+        const int p = r - HR;
+        return p >= -hb ? a.cw_in + (u.row0 + p) * CW : ringb + ((u.seq0 + p) % kRR) * CW;
+    };
+    if (tid < u.cnt) {
+        int c = 0;
+        for (int j = 0; j < tid; ++j) c += (fl[j] & 3) == kRecovered;
+        cord[tid] = c;
+    }
+    int nrec = 0;
+    for (int j = 0; j < u.cnt; ++j) nrec += (fl[j] & 3) == kRecovered;
+    const uint8_t* gco = a.coefs + static_cast<int64_t>(u.coef0) * kn;
+    if (nrec) burst_stage(smem, a.off_coef, gco, nrec * kn, tid, 256);
+    const uint8_t* coefs = smem + a.off_coef + static_cast<int>(reinterpret_cast<uintptr_t>(gco) & 3);
+    // dword w of row r (the row's bytes from its dword phase on): batches of loads in flight
+    auto stage_rows = [&](int nrows, auto src_of) {
+        for (int base = 0; base < nrows * CWD; base += 256 * 4) {
+            uint32_t v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int idx = base + q * 256 + tid;
+                v[q] = 0;
+                if (idx >= nrows * CWD) continue;
+                const int r = fdiv(a.dcwd, idx), w = idx - r * CWD;
+                const uint8_t* g = src_of(r);
+                if (!g) continue;
+                const int ph = static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
+                const int lo = 4 * w - ph;  // the dword's first byte in the row
+                if (lo >= CW) continue;
+                if (lo >= 0 && lo + 4 <= CW) {
+                    v[q] = *reinterpret_cast<const uint32_t*>(g + lo);
+                } else {
+                    for (int e = 0; e < 4; ++e)
+                        if (lo + e >= 0 && lo + e < CW) v[q] |= uint32_t(g[lo + e]) << (8 * e);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int idx = base + q * 256 + tid;
+                if (idx >= nrows * CWD) continue;
+                const int r = fdiv(a.dcwd, idx), w = idx - r * CWD;
+                *reinterpret_cast<uint32_t*>(smem + a.off_rows + r * CWS + 4 * w) = v[q];
+            }
+        }
+    };
+    stage_rows(HR + u.cnt, row_src);
+    __syncthreads();
+    // window byte h of output row j (packet x = seq0 + j - T = row j + k - 1)
+    auto byte_at = [&](int j, int h) -> uint8_t {
+        const int s = fdiv(a.dk, h), i = h - s * k;
+        if ((fl[j] & 3) == kCopy) {
+            const int ro = rowoff[j + k - 1];
+            return ro < 0 ? 0 : smem[ro + s * n + i];
+        }
+        const uint8_t* coef = coefs + cord[j] * kn + i * n;
+        uint8_t acc = 0;
+        for (int q = 0; q < n; ++q) {  // symbol q of packet x - i + q
+            const uint8_t c = coef[q];
+            const int r = j + k - 1 - i + q;
+            if (!c || r > j + HR) continue;
+            const int ro = rowoff[r];
+            if (ro >= 0) acc ^= gmul(gexp, glog, c, smem[ro + s * n + q]);
+        }
+        return acc;
+    };
+    if (tid < u.cnt) {  // header bytes first: they bound the copy
+        const int fate = fl[tid] & 3;
+        int ln = 0;
+        if (fate == kCopy || fate == kRecovered) {
+            const int hdr = byte_at(tid, 0) * 256 + byte_at(tid, 1);
+            ln = (fl[tid] & kRowClamp) ? min(hdr, L) : hdr;
+        }
+        lnS[tid] = ln;
+        cpS[tid] = min(ln, L);
+        a.out_len[u.row0 + tid] = ln;
+    }
+    __syncthreads();
+    uint8_t* gout = a.out + u.row0 * L;
+    const int ao = a.off_out + static_cast<int>(reinterpret_cast<uintptr_t>(gout) & 3);
+    for (int it = tid; it < u.cnt * LW; it += 256) {
+        const int j = fdiv(a.dlw, it), w = it - j * LW;
+        const int cp = cpS[j];
+        uint8_t* o = smem + ao + j * L + 4 * w;
+        if ((fl[j] & 3) == kCopy) {  // systematic bytes of the packet's own codeword
+            const int ro = rowoff[j + k - 1];
+            int s = fdiv(a.dk, 4 * w + 2), i = 4 * w + 2 - s * k;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int b = 4 * w + e;
+                if (b < L) o[e] = (b < cp && ro >= 0) ? smem[ro + s * n + i] : 0;
+                if (++i == k) i = 0, ++s;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int b = 4 * w + e;
+                if (b < L) o[e] = b < cp ? byte_at(j, b + 2) : 0;
+            }
+        }
+    }
+    __syncthreads();
+    burst_flush(gout, smem, ao, u.cnt * L, tid, 256);
+    if (u.lead != 0) return;
+    // the burst's last min(total, T + k) codewords into the ring (missing ones leave their slot as it is)
+    const int m = min(u.total, T + k), t0 = u.total - m;
+    int slot0 = HR + t0;  // LDS row of burst row t0
+    if (u.total > u.cnt) {  // they lie (partly) behind this chunk: staged again, rows 0 .. m-1
+        slot0 = 0;
+        for (int r = tid; r < m; r += 256) {
+            const uint8_t* g = a.cw_in + (u.row0 + t0 + r) * CW;
+            rowoff[r] = (a.flags[u.row0 + t0 + r] & kRowErased)
+                            ? -1 : a.off_rows + r * CWS + static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
+        }
+        __syncthreads();
+        auto tail_src = [&](int r) -> const uint8_t* {
+            return rowoff[r] < 0 ? nullptr : a.cw_in + (u.row0 + t0 + r) * CW;
+        };
+        stage_rows(m, tail_src);
+        __syncthreads();
+    }
+    for (int tt = tid >> 6; tt < m; tt += 4) {
+        const int ro = rowoff[slot0 + tt];
+        if (ro >= 0) burst_flush(ringb + ((u.seq0 + t0 + tt) % kRR) * CW, smem, ro, CW, tid & 63, 64);
+    }
+}
+
 }  // namespace
 }  // namespace fec
 
@@ -435,6 +829,7 @@ struct fec_streams {
     hipEvent_t staged[kStageBufs] = {};      // the last kernel (and upload) that read h_stage[b]
     int buf = 0;                             // the next call's buffer
     size_t stage_bytes = 0;
+    size_t stage_cap[kStageBufs] = {};       // bytes of h_stage[b] (a burst call grows its buffer to its records)
     hipEvent_t done = nullptr;               // the last call's kernel (windows, rings, older d_stage free)
     bool poisoned = false;                   // a failed call left host and device state apart
     ~fec_streams() {
@@ -482,6 +877,161 @@ int stage_free(fec_streams* h, hipStream_t s, int* b) {
     FS_TRY(hipEventSynchronize(h->staged[*b]));
     FS_TRY(hipStreamWaitEvent(s, h->done, 0));
     return FEC_OK;
+}
+
+
+// Staging buffer b (free: stage_free has waited for its last reader) holds at least `bytes`.
+int stage_reserve(fec_streams* h, int b, size_t bytes) {
+    if (bytes <= h->stage_cap[b]) return FEC_OK;
+    const size_t cap = std::max(bytes, 2 * h->stage_cap[b]);
+    if (h->d_stage[b]) {
+        FS_TRY(hipFree(h->d_stage[b]));
+        h->d_stage[b] = nullptr;
+    }
+    FS_TRY(hipHostFree(h->h_stage[b]));
+    h->h_stage[b] = nullptr;
+    h->m_stage[b] = nullptr;
+    h->stage_cap[b] = 0;
+    if (h->upload) FS_TRY(hipMalloc(&h->d_stage[b], cap));
+    FS_TRY(hipHostMalloc(&h->h_stage[b], cap, hipHostMallocMapped));
+    FS_TRY(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
+    h->stage_cap[b] = cap;
+    return FEC_OK;
+}
+
+constexpr int kBurstLds = 160 * 1024;  // dynamic LDS a burst kernel may take (a CU's whole LDS)
+constexpr int kBurstTP = 32;          // packets per chunk, LDS permitting (at least the packets a chunk needs in front)
+constexpr size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
+
+// A launch with more than 64 KB of dynamic LDS needs the kernel's limit raised first (once per size).
+int burst_lds_allow(const void* kernel, int lds, int* raised) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    if (lds <= 64 * 1024 || lds <= *raised) return FEC_OK;
+    FS_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    *raised = lds;
+    return FEC_OK;
+}
+
+// counts all >= 1; their sum and largest
+int check_counts(const int32_t* counts, int M, int64_t* R, int* maxc) {
+    *R = 0;
+    *maxc = 0;
+    for (int m = 0; m < M; ++m) {
+        if (counts[m] < 1) return FEC_ERR_ARG;
+        *R += counts[m];
+        *maxc = std::max(*maxc, counts[m]);
+    }
+    return FEC_OK;
+}
+
+// LDS carve-up of fec_streams_encode_burst_kernel for chunks of tp packets (fills a's geometry); its bytes
+int burst_enc_lds(const fec::Geometry& g, int tp, fec::BurstEncArgs* a) {
+    const int np = g.n - g.k, H = g.n - 1, SK = g.S * g.k;
+    a->L = g.L, a->k = g.k, a->n = g.n, a->S = g.S, a->CW = g.CW, a->SK = SK;
+    a->NS4 = (g.S + 3) / 4;
+    a->SP = 4 * a->NS4;
+    a->SKS = (SK + 7) & ~3;
+    a->W = std::max(1, H);
+    a->TP = tp;
+    a->ROWS = tp + H;
+    size_t off = align16(static_cast<size_t>(std::max(1, g.k * np)) * 32);
+    a->off_planes = static_cast<int>(off);
+    off = align16(off + static_cast<size_t>(g.k) * a->ROWS * a->SP);
+    a->off_io = static_cast<int>(off);
+    off = align16(off + std::max(static_cast<size_t>(a->ROWS) * g.L, static_cast<size_t>(tp) * g.CW) + 32);
+    a->off_ring = static_cast<int>(off);
+    off = align16(off + static_cast<size_t>(H) * a->SKS);
+    a->off_len = static_cast<int>(off);
+    off = align16(off + static_cast<size_t>(a->ROWS) * 4);
+    a->dk = fec::fast_div(g.k);
+    a->dns4 = fec::fast_div(a->NS4);
+    a->dnq = fec::fast_div((SK + 3) >> 2);
+    return static_cast<int>(std::min<size_t>(off, 1u << 30));
+}
+
+int burst_dec_lds(const fec::Geometry& g, int tp, fec::BurstDecArgs* a) {
+    a->L = g.L, a->k = g.k, a->n = g.n, a->CW = g.CW, a->T = g.T;
+    a->CWD = (g.CW + 6) >> 2;
+    a->CWS = 4 * a->CWD;
+    a->LW = (g.L + 3) >> 2;
+    a->TP = tp;
+    a->HR = g.T + g.k - 1;
+    a->ROWS = a->HR + tp;
+    size_t off = 768;
+    a->off_rows = static_cast<int>(off);
+    off = align16(off + static_cast<size_t>(a->ROWS) * a->CWS);
+    a->off_coef = static_cast<int>(off);
+    off = align16(off + static_cast<size_t>(tp) * g.k * g.n + 16);
+    a->off_out = static_cast<int>(off);
+    off = align16(off + static_cast<size_t>(tp) * g.L + 32);
+    a->off_meta = static_cast<int>(off);
+    off = align16(off + static_cast<size_t>(a->ROWS) * 4 + static_cast<size_t>(tp) * 13);
+    a->dk = fec::fast_div(g.k);
+    a->dlw = fec::fast_div(a->LW);
+    a->dcwd = fec::fast_div(a->CWD);
+    return static_cast<int>(std::min<size_t>(off, 1u << 30));
+}
+
+// Packets per chunk for a call whose longest burst has maxc packets: at most kBurstTP (or maxc), at
+// least `front` (the packets a chunk needs in front of it, so that only a burst's first chunk reads
+// the ring), and within kBurstLds.  0: this geometry does not fit.
+template <class Args, class F>
+int burst_chunk(const fec::Geometry& g, int maxc, int front, F lds_of, Args* a, int* lds) {
+    if (g.S * g.k > 16384 || g.CW > 16384) return 0;
+    const int lo = std::max(1, front);
+    for (int tp = std::max(lo, std::min(maxc, kBurstTP)); tp >= lo; --tp) {
+        *lds = lds_of(g, tp, a);
+        if (*lds <= kBurstLds) return tp;
+    }
+    return 0;
+}
+
+// The call's chunks: bursts in row order, each cut every tp rows.  seq: packets of each stream so far.
+int64_t burst_units(const int32_t* counts, int M, int tp) {
+    int64_t nu = 0;
+    for (int m = 0; m < M; ++m) nu += (counts[m] + tp - 1) / tp;
+    return nu;
+}
+void burst_fill_units(fec::BurstUnit* u, const int32_t* ids, const int32_t* counts, int m0, int m1, int64_t row,
+                      int tp, const std::vector<int64_t>& seq) {
+    for (int m = m0; m < m1; ++m) {
+        for (int lead = 0; lead < counts[m]; lead += tp, ++u) {
+            u->row0 = row + lead;
+            u->seq0 = seq[ids[m]] + lead;
+            u->id = ids[m];
+            u->cnt = std::min(tp, counts[m] - lead);
+            u->lead = lead;
+            u->total = counts[m];
+            u->coef0 = 0;
+            u->pad = 0;
+        }
+        row += counts[m];
+    }
+}
+
+// The symbolic half of a burst for one stream: packets seq0 .. seq0 + count - 1 with erasure flags
+// er[]; one flag byte per row (the fate of packet seq - T | kRowClamp | kRowErased) and the k x n
+// blocks of the recovered rows, appended in row order.  A run of received packets on the fast path
+// is one skip_received, not a step each.
+void plan_burst_rows(fec::StreamPlanner& pl, int T, int kn, int64_t seq0, const uint8_t* er, int64_t count,
+                          uint8_t* flags, std::vector<uint8_t>& coefs) {
+    int64_t t = 0;
+    while (t < count) {
+        const int64_t seq = seq0 + t;
+        if (!er[t] && pl.fast_at(seq)) {
+            int64_t e = t + 1;
+            while (e < count && !er[e]) ++e;
+            pl.skip_received(seq, e - t);
+            for (int64_t i = t; i < e; ++i) flags[i] = seq0 + i >= T ? fec::kCopy : fec::kNone;
+            t = e;
+            continue;
+        }
+        const fec::StepResult r = pl.step(seq, er[t] != 0);
+        flags[t] = static_cast<uint8_t>(r.fate | (r.slow ? fec::kRowClamp : 0) | (er[t] ? fec::kRowErased : 0));
+        if (r.fate == fec::kRecovered) coefs.insert(coefs.end(), r.coef, r.coef + kn);
+        ++t;
+    }
 }
 
 }  // namespace
@@ -581,6 +1131,7 @@ int fec_streams_create(int max_payload, int T, int B, int N, int nstreams, fec_s
             if (h->upload) FS_TRY(hipMalloc(&h->d_stage[b], h->stage_bytes));
             FS_TRY(hipHostMalloc(&h->h_stage[b], h->stage_bytes, hipHostMallocMapped));
             FS_TRY(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
+            h->stage_cap[b] = h->stage_bytes;
             FS_TRY(hipEventCreateWithFlags(&h->staged[b], hipEventDisableTiming));
             FS_TRY(hipEventRecord(h->staged[b], nullptr));
         }
@@ -752,6 +1303,204 @@ int fec_streams_decode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
                      us(t0, t1), us(t1, t2), us(t2, t3), us(t3, t4));
     }
     return FEC_OK;
+}
+
+int fec_streams_encode_burst(fec_streams* h, const int32_t* ids, const int32_t* counts, int M,
+                             const uint8_t* d_payload, const int32_t* d_payload_len, uint8_t* d_codeword,
+                             int32_t* d_codeword_len, void* stream) {
+    if (!h || M < 0 || M > h->nstreams ||
+        (M > 0 && (!ids || !counts || !d_payload || !d_codeword || !d_codeword_len)))
+        return FEC_ERR_ARG;
+    if (M == 0) return FEC_OK;
+    int64_t R = 0;
+    int maxc = 0;
+    if (int st = check_counts(counts, M, &R, &maxc)) return st;
+    if (maxc == 1)  // one packet per stream: the one-packet kernel
+        return fec_streams_encode(h, ids, M, d_payload, d_payload_len, d_codeword, d_codeword_len, stream);
+    if (int st = check_ids(h, ids, M)) return st;
+    fec::BurstEncArgs a;
+    int lds = 0;
+    const int tp = burst_chunk(h->g, maxc, h->g.n - 1, burst_enc_lds, &a, &lds);
+    if (tp == 0) return FEC_ERR_ARG;
+    const int64_t nu = burst_units(counts, M, tp);
+    if (nu > INT32_MAX) return FEC_ERR_ARG;
+    static int lds_raised = 0;
+    if (int st = burst_lds_allow(reinterpret_cast<const void*>(fec::fec_streams_encode_burst_kernel), lds, &lds_raised))
+        return st;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int b = 0;
+    if (int st = stage_free(h, s, &b)) return st;
+    const size_t bytes = static_cast<size_t>(nu) * sizeof(fec::BurstUnit);
+    if (int st = stage_reserve(h, b, bytes)) {
+        h->poisoned = true;  // the buffer may be gone
+        return st;
+    }
+    burst_fill_units(static_cast<fec::BurstUnit*>(h->h_stage[b]), ids, counts, 0, M, 0, tp, h->enc_seq);
+    if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
+    fec::CodecView v;
+    fec::codec_view(h->codec, &v);
+    a.payload = d_payload;
+    a.len = d_payload_len;
+    a.units = static_cast<const fec::BurstUnit*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
+    a.win = h->d_win;
+    a.cw = d_codeword;
+    a.cw_len = d_codeword_len;
+    a.ptab = v.ptab;
+    hipLaunchKernelGGL(fec::fec_streams_encode_burst_kernel, dim3(static_cast<unsigned>(nu)), dim3(256), lds, s, a);
+    FS_TRY(hipGetLastError());
+    FS_TRY(hipEventRecord(h->done, s));
+    FS_TRY(hipEventRecord(h->staged[b], s));
+    h->buf = (b + 1) % fec_streams::kStageBufs;
+    for (int m = 0; m < M; ++m) h->enc_seq[ids[m]] += counts[m];
+    return FEC_OK;
+}
+
+int fec_streams_decode_burst(fec_streams* h, const int32_t* ids, const int32_t* counts, int M,
+                             const uint8_t* erasure, const uint8_t* d_codeword, uint8_t* d_payload_out,
+                             int32_t* d_payload_len, void* stream) {
+    if (!h || M < 0 || M > h->nstreams ||
+        (M > 0 && (!ids || !counts || !erasure || !d_codeword || !d_payload_out || !d_payload_len)))
+        return FEC_ERR_ARG;
+    if (M == 0) return FEC_OK;
+    int64_t R = 0;
+    int maxc = 0;
+    if (int st = check_counts(counts, M, &R, &maxc)) return st;
+    if (maxc == 1)  // one packet per stream: the one-packet kernel
+        return fec_streams_decode(h, ids, M, erasure, d_codeword, d_payload_out, d_payload_len, stream);
+    if (int st = check_ids(h, ids, M)) return st;
+    const fec::Geometry& g = h->g;
+    fec::BurstDecArgs a;
+    int lds = 0;
+    const int tp = burst_chunk(g, maxc, g.T + g.k - 1, burst_dec_lds, &a, &lds);
+    if (tp == 0) return FEC_ERR_ARG;
+    const int64_t nu = burst_units(counts, M, tp);
+    if (nu > INT32_MAX) return FEC_ERR_ARG;
+    static int lds_raised = 0;
+    if (int st = burst_lds_allow(reinterpret_cast<const void*>(fec::fec_streams_decode_burst_kernel), lds, &lds_raised))
+        return st;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int b = 0;
+    if (int st = stage_free(h, s, &b)) return st;
+    const int kn = g.k * g.n;
+    // The symbolic decoders advance before the launch: a failure from here on leaves the host planners
+    // ahead of the device rings, and the group refuses every later call.
+    struct Poison {
+        fec_streams* h;
+        bool armed = true;
+        ~Poison() { if (armed) h->poisoned = true; }
+    } poison{h};
+    try {
+        // streams are independent: contiguous parts of them, one per thread; a part's recovered rows
+        // keep their coefficient blocks in row order
+        // (the pool calls every one of its parts: a call with fewer streams than parts leaves some empty)
+        const int np = (h->pool && R >= 2 * kPoolMinItems) ? h->pool->parts() : 1;
+        std::vector<int64_t> row_at(M + 1, 0), unit_at(M + 1, 0);
+        for (int m = 0; m < M; ++m) {
+            row_at[m + 1] = row_at[m] + counts[m];
+            unit_at[m + 1] = unit_at[m] + (counts[m] + tp - 1) / tp;
+        }
+        std::vector<uint8_t> flags(static_cast<size_t>(R));
+        std::vector<fec::BurstUnit> units(static_cast<size_t>(nu));
+        std::vector<std::vector<uint8_t>> coefs(np);
+        std::atomic<bool> failed{false};
+        auto part = [&](int p) {
+            if (p < 0 || p >= np) return;
+            try {
+                const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
+                const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
+                burst_fill_units(units.data() + unit_at[m0], ids, counts, m0, m1, row_at[m0], tp, h->dec_seq);
+                int32_t nrec = 0;
+                for (int m = m0; m < m1; ++m) {
+                    const int id = ids[m];
+                    plan_burst_rows(*h->planners[id], g.T, kn, h->dec_seq[id], erasure + row_at[m], counts[m],
+                                         flags.data() + row_at[m], coefs[p]);
+                    h->dec_seq[id] += counts[m];
+                    for (int64_t ui = unit_at[m]; ui < unit_at[m + 1]; ++ui) {
+                        fec::BurstUnit& u = units[ui];
+                        u.coef0 = nrec;
+                        for (int j = 0; j < u.cnt; ++j) nrec += (flags[u.row0 + j] & 3) == fec::kRecovered;
+                    }
+                }
+            } catch (...) {
+                failed.store(true);
+            }
+        };
+        if (np > 1)
+            h->pool->run(part);
+        else
+            part(0);
+        if (failed.load()) return FEC_ERR_ARG;
+        // staging: units | row flags | coefficient blocks
+        const size_t off_flags = align16(static_cast<size_t>(nu) * sizeof(fec::BurstUnit));
+        const size_t off_coef = align16(off_flags + static_cast<size_t>(R));
+        size_t ncoef = 0;
+        for (const auto& c : coefs) ncoef += c.size();
+        if (ncoef / kn > INT32_MAX) return FEC_ERR_ARG;
+        const size_t bytes = off_coef + ncoef + 16;
+        if (int st = stage_reserve(h, b, bytes)) return st;
+        uint8_t* hs = static_cast<uint8_t*>(h->h_stage[b]);
+        size_t cbase = 0;
+        for (int p = 0; p < np; ++p) {  // a part's blocks follow those of the parts before it
+            const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
+            const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
+            if (cbase)
+                for (int64_t ui = unit_at[m0]; ui < unit_at[m1]; ++ui) units[ui].coef0 += static_cast<int32_t>(cbase / kn);
+            if (!coefs[p].empty()) std::memcpy(hs + off_coef + cbase, coefs[p].data(), coefs[p].size());
+            cbase += coefs[p].size();
+        }
+        std::memcpy(hs, units.data(), units.size() * sizeof(fec::BurstUnit));
+        std::memcpy(hs + off_flags, flags.data(), flags.size());
+        if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
+        const uint8_t* rec = static_cast<const uint8_t*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
+        fec::CodecView v;
+        fec::codec_view(h->codec, &v);
+        a.cw_in = d_codeword;
+        a.units = reinterpret_cast<const fec::BurstUnit*>(rec);
+        a.flags = rec + off_flags;
+        a.coefs = rec + off_coef;
+        a.ring = h->d_ring;
+        a.gf = v.gf;
+        a.out = d_payload_out;
+        a.out_len = d_payload_len;
+        hipLaunchKernelGGL(fec::fec_streams_decode_burst_kernel, dim3(static_cast<unsigned>(nu)), dim3(256), lds, s, a);
+        FS_TRY(hipGetLastError());
+        FS_TRY(hipEventRecord(h->done, s));
+        FS_TRY(hipEventRecord(h->staged[b], s));
+        h->buf = (b + 1) % fec_streams::kStageBufs;
+        poison.armed = false;
+        return FEC_OK;
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    } catch (...) {
+        return FEC_ERR_ARG;
+    }
+}
+
+int fec_streams_plan_burst_host(int max_payload, int T, int B, int N, const uint8_t* erasure,
+                                const int32_t* counts, int ncounts, uint8_t* fate) {
+    if (!erasure || !fate || !counts || ncounts < 0) return FEC_ERR_ARG;
+    try {
+        const fec::Geometry g = fec::Geometry::make(max_payload, T, B, N);
+        if (g.B < g.N || g.n > fec::kMaxN - 1) return FEC_ERR_ARG;  // fec_plan_host's bounds
+        int64_t P = 0;
+        int maxc = 0;
+        if (int st = check_counts(counts, ncounts, &P, &maxc)) return st;
+        const auto rules = fec::shared_decode_rules(T, B, N);
+        fec::StreamPlanner pl(g, rules.get());
+        std::vector<uint8_t> flags(static_cast<size_t>(P)), coefs;
+        int64_t seq = 0;
+        for (int c = 0; c < ncounts; ++c) {
+            coefs.clear();
+            plan_burst_rows(pl, g.T, g.k * g.n, seq, erasure + seq, counts[c], flags.data() + seq, coefs);
+            seq += counts[c];
+        }
+        for (int64_t t = g.T; t < P; ++t) fate[t - g.T] = flags[t] & 3;
+        return FEC_OK;
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    } catch (...) {
+        return FEC_ERR_ARG;
+    }
 }
 
 int fec_streams_state(const fec_streams* h, int id, int64_t* sent, int64_t* received) {

@@ -181,6 +181,41 @@ int fec_streams_encode(fec_streams *group, const int32_t *ids, int M, const uint
 int fec_streams_decode(fec_streams *group, const int32_t *ids, int M, const uint8_t *erasure,
                        const uint8_t *d_codeword, uint8_t *d_payload_out, int32_t *d_payload_len,
                        void *hip_stream);
+/* Bursts: one call hands over counts[m] >= 1 consecutive packets of each of M distinct streams
+ * (ids, counts: host arrays).  With R = the sum of the counts, every row array has R rows (payload,
+ * sizes, codewords, the host erasure flags, the outputs), stream ids[m]'s rows starting at row
+ * counts[0] + ... + counts[m-1], its next counts[m] packets in order.  A call equals counts[m]
+ * one-packet calls per stream, byte for byte and in the group's state afterwards, and bursts and
+ * one-packet calls on one group continue each other; R is not bounded by nstreams.  The burst
+ * kernels (fec_streams.hip) cut a burst into chunks of up to 32 packets, one workgroup each: a
+ * chunk takes the packets in front of it from the call's own rows, the stream's state in HBM is
+ * read by a burst's first chunk only and written once per burst (the last n-1 windows, the last
+ * T+k codewords); parity runs on packed 4-byte GF tables over LDS, a received row costs one
+ * staged byte, only recovered rows carry a coefficient block.  Measured on an MI355X at 10 000
+ * streams of (10,3,3), 300-byte payloads, encode + decode with the host's symbolic steps
+ * (tools/streams_burst_ab.py, profiles/streams_burst/): 12.2 ns per packet one packet per call,
+ * 8.9 ns in bursts of 4, 3.43 ns in bursts of 16, 2.67 ns in bursts of 64; the burst kernels
+ * alone run at 0.07 - 0.11 of the 8.0 TB/s peak over L + CW / CW + 1 + L bytes per packet.
+ * FEC_ERR_ARG (group unchanged): repeated or out-of-range id, count < 1, null pointer, or a
+ * geometry whose smallest chunk does not fit a CU's 160 KB of LDS: an encode chunk holds
+ * 2(n-1) windows as position planes plus the larger of 2(n-1) payload rows and n-1 codewords plus
+ * n-1 ring windows, a decode chunk 2(T+k-1) codewords plus T+k-1 payload rows and k x n blocks --
+ * (10,3,3) fits at every max_payload a group takes (up to 1 500 bytes; 99 KB for the decode
+ * chunk there), (24,12,12) at 1 500 bytes does not.  Any other failure
+ * after the arguments passed (a HIP call, among them growing the pinned staging buffer to the
+ * call, or memory for the decode's records) poisons the group like a failed one-packet decode:
+ * every later call returns FEC_ERR_HIP. */
+int fec_streams_encode_burst(fec_streams *group, const int32_t *ids, const int32_t *counts, int M,
+                             const uint8_t *d_payload, const int32_t *d_payload_len,
+                             uint8_t *d_codeword, int32_t *d_codeword_len, void *hip_stream);
+int fec_streams_decode_burst(fec_streams *group, const int32_t *ids, const int32_t *counts, int M,
+                             const uint8_t *erasure, const uint8_t *d_codeword,
+                             uint8_t *d_payload_out, int32_t *d_payload_len, void *hip_stream);
+/* Host only, no device: the symbolic half of fec_streams_decode_burst for one stream fed its
+ * packets in bursts of counts[0 .. ncounts-1] -- fate[x] for packets 0 .. sum(counts)-T-1 in
+ * fec_plan_host's encoding, through the routine the decode call builds its records with. */
+int fec_streams_plan_burst_host(int max_payload, int T, int B, int N, const uint8_t *erasure,
+                                const int32_t *counts, int ncounts, uint8_t *fate);
 /* Packets stream `id` has sent (encoded) and received (decoded) so far. */
 int fec_streams_state(const fec_streams *group, int id, int64_t *sent, int64_t *received);
 
