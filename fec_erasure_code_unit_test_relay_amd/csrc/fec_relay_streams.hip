@@ -1,0 +1,654 @@
+// fec_relay_streams.hip -- the symbol-wise decode-and-forward relay (RELAYING_TYPE 2) and its
+// destination for many independent relay streams of one (max_payload, T1, N1, T2, N2), one packet or
+// a burst of each named stream per call, in one launch.
+//
+// Reference: one Decoder_Symbol_Wise per stream and side (src/Decoder_Symbol_Wise.cpp), fed one
+// packet per call by Variable_Rate_FEC_Decoder (relay :950-1601, destination :1603-1879):
+// push_current_codeword / rotate_pointers_and_insert_zero_word (:119-176), then
+// symbol_wise_encode_1 (:547-619) at the relay or symbol_wise_decode_1 + extract_data (:621-665) at
+// the destination.  The arithmetic, the frame layout and the undefined behaviour defined away are
+// those of fec_swdf.hip (its head comment), whose batched calls run a fresh chain over seqs 0..P-1;
+// here a group keeps every stream's chain between calls.
+//
+// What a seq needs.  With the decode done in place on the received rows (the data symbol (j, m) of
+// row r belongs to the diagonal of packet r+n-1-m alone), the relay's frame symbol (j, p) of seq t
+// reads the decoded hop-1 row t-p-n1+k; the symbols it reads there are decoded by the packets
+// t-n2+1 .. t, whose windows reach back to row t-n1-n2+2.  The destination's row for seq t reads
+// the decoded frames t-n2+1 .. t.
+//
+// State in HBM, per stream (zero at create: the slots before a stream's first packet are zero and
+// not erased):
+//   * relay side: a ring of the last H1 = n1+n2-2 hop-1 codewords (rows of S*n1 bytes, zero for an
+//     erased packet), slot seq % H1.  The forwarded rows Y are recomputed from it, not kept: a ring
+//     of Y would have to be written with the burst's last n2-1 forwarded rows, which another
+//     workgroup (the burst's last chunk) computes, while the codewords of any chunk are in the
+//     call's own rows; and in the window without erasure Y is a permutation of the codewords, so
+//     recomputing it costs no arithmetic;
+//   * destination side: a ring of the symbol parts (S*n2 bytes from frame byte 4) of the last
+//     H2 = n2-1 frames, slot seq % H2.
+// State on the host, per stream and side: the seq counter and the flags of the last 64 seqs as a
+// shift register (bit 63 = the newest); the window mask of a row is its top n bits.
+//
+// A call's bursts are cut into chunks of at most TP packets, one workgroup each.  A chunk stages the
+// H rows in front of it and its own rows in LDS.  A burst's first chunk takes the rows in front from
+// the stream's ring; every later chunk lies at least H rows into the burst (TP >= H whenever a burst
+// has more than one chunk) and takes them from the call's own rows.  The first chunk's workgroup
+// alone writes the ring, after the barrier behind its staging, with the burst's last min(total, H)
+// rows (from the call's rows, zero for an erased one).  So no workgroup reads a ring row that
+// another workgroup of the launch writes, and a burst longer than the ring writes no slot twice
+// (min(total, H) consecutive seqs, H slots).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "fec_amd.h"
+#include "fec_device.h"
+#include "fec_host.h"
+#include "fec_kernels.h"
+#include "fec_status.h"
+
+namespace fec {
+namespace {
+
+constexpr int kRsThreads = 256;
+constexpr int kRsTP = 32;             // packets per chunk, LDS permitting
+constexpr int kRsLds = 160 * 1024;    // a CU's LDS
+constexpr int kRsMaxD = 64;           // decoded packets of a chunk: n2-1 + TP <= 16 + 32; rows: H + TP <= 64
+constexpr int kRsRuleU16 = 16 + 16 * 17;  // a wave's rule: sel[k], log col[k][n]
+// fixed part of the LDS: exp (1040), log16 (512), masks, row states, the four waves' rules
+constexpr int kRsOffMask = 1552, kRsOffRow = kRsOffMask + 4 * kRsMaxD, kRsOffRule = kRsOffRow + kRsMaxD;
+constexpr int kRsOffTab = kRsOffRule + 4 * 2 * kRsRuleU16;
+static_assert(kRsOffTab % 16 == 0, "LDS carve-up");
+
+struct RsUnit {      // one chunk = one workgroup
+    int64_t row0;    // its first row in the call's row arrays
+    int64_t seq0;    // that row's sequence number in its stream
+    int32_t id;
+    int32_t cnt;     // rows of the chunk (<= TP)
+    int32_t lead;    // rows of the burst in front of the chunk (0: the first chunk)
+    int32_t total;   // rows of the burst
+    uint32_t hist;   // first chunk: flags of the H seqs in front of the burst (bit i = seq0 - H + i)
+    int32_t pad;
+};
+
+struct RsArgs {
+    const uint8_t* in;      // R rows of in_stride bytes; symbol (row, j, m) at in_off + j*n + m
+    int64_t in_stride;
+    int in_off;
+    const RsUnit* units;
+    const uint32_t* masks;  // R window masks (bit m = flag of seq t-n+1+m)
+    uint8_t* ring;          // [streams][H][RB]
+    const uint8_t* rules;   // window-n rule table (raw coefficients)
+    const uint8_t* gf;      // exp[512], log[256]
+    const uint32_t* tab;    // relay: gf_mul4x tables of G2[k-1-m][p], [(p-k)*k + m][5]
+    uint8_t* out;           // relay: R frames of out_row = F bytes; destination: R rows of S*k
+    uint8_t* flag;          // R bytes (may be null)
+    int k, n, n2, S, S4, blocks, ES;
+    int H;                  // rows staged in front of a chunk
+    int D0;                 // packets decoded in front of a chunk (relay: n2-1, destination: 0)
+    int RB, RS;             // row bytes S*n; LDS row stride
+    int out_row;
+    int off_raw, off_ct;    // LDS carve-up after the tables
+};
+
+// One workgroup per chunk.  LDS: GF tables; the masks of the decoded packets; per staged row its
+// state; the rows as in memory (later the chunk's output rows); CT[row][m][g] = the data symbols
+// m < k of the row as words of four blocks 4g..4g+3 (zero for an erased row, a row before seq 0 and
+// the blocks past `blocks`).  Local row l is seq seq0 - H + l; decoded packet d is seq seq0 - D0 + d
+// and its diagonal's position c sits in local row d + c (H - D0 = n - 1 on both sides).
+template <bool RELAY>
+__global__ __launch_bounds__(kRsThreads) void fec_relay_streams_kernel(RsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    // exp[0..509] then zeros to 1039; log16[x] = log x, 512 for x = 0: exp[log16 a + log16 b] = a*b
+    uint8_t* gexp = smem;
+    uint16_t* glog16 = reinterpret_cast<uint16_t*>(smem + 1040);
+    uint32_t* pm = reinterpret_cast<uint32_t*>(smem + kRsOffMask);
+    uint8_t* rst = smem + kRsOffRow;  // 0: a zero row (erased / before seq 0); else 1 + the staged row's byte phase
+    uint32_t* tb = reinterpret_cast<uint32_t*>(smem + kRsOffTab);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint16_t* rl = reinterpret_cast<uint16_t*>(smem + kRsOffRule) + wave * kRsRuleU16;
+    const RsUnit u = a.units[blockIdx.x];
+    const int k = a.k, n = a.n, S = a.S, S4 = a.S4, G = S4 >> 2, H = a.H, D0 = a.D0, RB = a.RB, RS = a.RS;
+    const int rows = H + u.cnt, nd = D0 + u.cnt, ctrow = k * S4, blocks = a.blocks;
+    const bool first = u.lead == 0;  // the rows in front come from the ring
+    uint8_t* ringb = a.ring + static_cast<int64_t>(u.id) * H * RB;
+    for (int i = tid; i < 1040; i += kRsThreads) gexp[i] = i < 510 ? a.gf[i] : 0;
+    for (int i = tid; i < 256; i += kRsThreads) glog16[i] = i ? a.gf[512 + i] : 512;
+    if constexpr (RELAY)
+        for (int i = tid; i < (a.n2 - k) * k * 5; i += kRsThreads) tb[i] = a.tab[i];
+    auto row_src = [&](int l) -> const uint8_t* {  // local row l < H of a first chunk: the ring's
+        const int p = l - H;
+        return (p >= 0 || !first) ? a.in + (u.row0 + p) * a.in_stride + a.in_off
+                                  : ringb + ((u.seq0 + p) % H) * RB;
+    };
+    for (int l = tid; l < rows; l += kRsThreads) {
+        const int p = l - H;
+        bool live;
+        if (p >= 0 || !first)
+            live = !((a.masks[u.row0 + p] >> (n - 1)) & 1u);  // a row's own flag is its mask's top bit
+        else
+            live = u.seq0 + p >= 0;  // (an erased packet's ring row is zero)
+        rst[l] = live ? 1 + static_cast<int>(reinterpret_cast<uintptr_t>(row_src(l)) & 3) : 0;
+    }
+    const uint32_t nbits = n >= 32 ? ~0u : (1u << n) - 1u;
+    for (int d = tid; d < nd; d += kRsThreads) {
+        const int p = d - D0;
+        const uint32_t m = (p >= 0 || !first) ? a.masks[u.row0 + p] : (static_cast<uint32_t>(u.hist >> d) & nbits);
+        pm[d] = m;
+        if (p >= 0 && a.flag) a.flag[u.row0 + p] = __popc(m) >= n - k + 1 ? 1 : 0;
+    }
+    __syncthreads();
+    // 1. the rows into LDS, a wave per row (rows of erased packets are never read)
+    for (int l = wave; l < rows; l += kRsThreads / 64)
+        if (rst[l]) burst_stage(smem, a.off_raw + l * RS, row_src(l), RB, lane, 64);
+    __syncthreads();
+    // 2. CT, a wave per row
+    for (int l = wave; l < rows; l += kRsThreads / 64) {
+        const int st = rst[l];
+        const uint32_t rowp = a.off_raw + l * RS + (st - 1);
+        for (int it = lane; it < k * G; it += 64) {
+            const int m = it / G, g = it - m * G;
+            uint32_t w = 0;
+            if (st) {
+                const uint32_t src = rowp + m + 4 * g * n;  // (blocks past S: bytes of the slack, masked off)
+                w = (uint32_t(smem[src]) | uint32_t(smem[src + n]) << 8 | uint32_t(smem[src + 2 * n]) << 16 |
+                     uint32_t(smem[src + 3 * n]) << 24) & keep_bytes(blocks - 4 * g);
+            }
+            *reinterpret_cast<uint32_t*>(smem + a.off_ct + l * ctrow + m * S4 + 4 * g) = w;
+        }
+    }
+    __syncthreads();
+    // 3. decodeBlock(T = n-1, t = 0) of every packet whose window holds 0 < erasures < n-k+1, through
+    // the window-n rule of its mask, in place: a wave per packet, a lane per word of four blocks.  A
+    // recovered symbol m lands in CT[d + m][m], which no other packet and no later symbol reads
+    // (position m is erased).
+    for (int d = wave; d < nd; d += kRsThreads / 64) {
+        const uint32_t mask = pm[d];
+        const int cnt = __popc(mask);
+        if (cnt == 0 || cnt >= n - k + 1) continue;
+        const uint8_t* e = a.rules + static_cast<int64_t>(mask) * a.ES;
+        for (int i = lane; i < k + k * n; i += 64) rl[i] = i < k ? e[i] : glog16[e[i]];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (int m = 0; m < k; ++m) {
+            if (!((mask >> m) & 1u) || rl[m] == 0xFF) continue;
+            for (int g = lane; g < G; g += 64) {
+                uint32_t acc = 0;
+                for (int c = 0; c < n; ++c) {
+                    const int st = rst[d + c];
+                    if (((mask >> c) & 1u) || !st) continue;  // an erased symbol is zero
+                    uint32_t x;
+                    if (c < k) {
+                        x = *reinterpret_cast<const uint32_t*>(smem + a.off_ct + (d + c) * ctrow + c * S4 + 4 * g);
+                    } else {
+                        const uint32_t src = a.off_raw + (d + c) * RS + (st - 1) + c + 4 * g * n;
+                        x = (uint32_t(smem[src]) | uint32_t(smem[src + n]) << 8 | uint32_t(smem[src + 2 * n]) << 16 |
+                             uint32_t(smem[src + 3 * n]) << 24) & keep_bytes(blocks - 4 * g);
+                    }
+                    const int lc = rl[k + m * n + c];
+                    acc ^= uint32_t(gexp[lc + glog16[x & 255]]) | uint32_t(gexp[lc + glog16[(x >> 8) & 255]]) << 8 |
+                           uint32_t(gexp[lc + glog16[(x >> 16) & 255]]) << 16 | uint32_t(gexp[lc + glog16[x >> 24]]) << 24;
+                }
+                *reinterpret_cast<uint32_t*>(smem + a.off_ct + (d + m) * ctrow + m * S4 + 4 * g) = acc;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the rule slot is reused by the wave's next packet
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
+    // 4. the chunk's output rows into LDS, over the staged rows (all reads of them are done), at the
+    // byte phase of their place in memory; words of four blocks, scattered to the blocks' bytes
+    const int orow = a.out_row;
+    uint8_t* gout = a.out + u.row0 * orow;
+    const int ao = a.off_raw + static_cast<int>(reinterpret_cast<uintptr_t>(gout) & 3);
+    if constexpr (RELAY) {
+        // frame = [size BE16][0, 0][S blocks of n2][n2-2 zeros]; symbol (j, p) = XOR_m G2[k-1-m][p] *
+        // CT[row t-p-n1+k][m][j]: a copy of m = k-1-p for p < k (G2 = [I | P])
+        const int n2 = a.n2, size = (S + 1) * n2;
+        for (int t = tid; t < u.cnt; t += kRsThreads) {
+            uint8_t* f = smem + ao + t * orow;
+            f[0] = uint8_t(size >> 8);
+            f[1] = uint8_t(size);
+            f[2] = 0;
+            f[3] = 0;
+            for (int b = 4 + S * n2; b < orow; ++b) f[b] = 0;
+        }
+        for (int p = 0; p < n2; ++p) {
+            for (int it = tid; it < u.cnt * G; it += kRsThreads) {
+                const int t = it / G, g = it - t * G;
+                const uint32_t src = a.off_ct + (t + n2 - 2 - p + k) * ctrow + 4 * g;  // local row of seq t-p-n1+k
+                uint32_t w = 0;
+                if (p < k) {
+                    w = *reinterpret_cast<const uint32_t*>(smem + src + (k - 1 - p) * S4);
+                } else {
+                    for (int m = 0; m < k; ++m)
+                        w ^= gf_mul4x(tb + ((p - k) * k + m) * 5, *reinterpret_cast<const uint32_t*>(smem + src + m * S4));
+                }
+                uint8_t* o = smem + ao + t * orow + 4 + p + 4 * g * n2;
+                const int ne = min(4, S - 4 * g);
+                o[0] = uint8_t(w);
+                if (ne > 1) o[n2] = uint8_t(w >> 8);
+                if (ne > 2) o[2 * n2] = uint8_t(w >> 16);
+                if (ne > 3) o[3 * n2] = uint8_t(w >> 24);
+            }
+        }
+    } else {
+        // out[t][j*k + i] = d_t[k-1-i][j] = CT[row t-n2+k-i][k-1-i][j]
+        for (int i = 0; i < k; ++i) {
+            for (int it = tid; it < u.cnt * G; it += kRsThreads) {
+                const int t = it / G, g = it - t * G;
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(smem + a.off_ct + (t + k - 1 - i) * ctrow +
+                                                                      (k - 1 - i) * S4 + 4 * g);
+                uint8_t* o = smem + ao + t * orow + i + 4 * g * k;
+                const int ne = min(4, S - 4 * g);
+                o[0] = uint8_t(w);
+                if (ne > 1) o[k] = uint8_t(w >> 8);
+                if (ne > 2) o[2 * k] = uint8_t(w >> 16);
+                if (ne > 3) o[3 * k] = uint8_t(w >> 24);
+            }
+        }
+    }
+    __syncthreads();
+    burst_flush(gout, smem, ao, u.cnt * orow, tid, kRsThreads);
+    if (!first) return;
+    // 5. the burst's last min(total, H) rows into the ring (the ring's rows were read in step 1),
+    // through LDS: the call's rows again (they may lie behind this chunk), zero for an erased one
+    __syncthreads();
+    const int nr = min(u.total, H), t0 = u.total - nr;
+    for (int r = wave; r < nr; r += kRsThreads / 64) {
+        const int64_t row = u.row0 + t0 + r;
+        const uint8_t* g = a.in + row * a.in_stride + a.in_off;
+        const bool erased = (a.masks[row] >> (n - 1)) & 1u;
+        if (erased) {
+            for (int w = lane; 4 * w < RS; w += 64) *reinterpret_cast<uint32_t*>(smem + a.off_raw + r * RS + 4 * w) = 0;
+        } else {
+            burst_stage(smem, a.off_raw + r * RS, g, RB, lane, 64);
+        }
+        if (lane == 0) rst[r] = erased ? 0 : static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);  // the row's byte phase
+    }
+    __syncthreads();
+    for (int r = wave; r < nr; r += kRsThreads / 64)
+        burst_flush(ringb + ((u.seq0 + t0 + r) % H) * RB, smem, a.off_raw + r * RS + rst[r], RB, lane, 64);
+}
+
+constexpr size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
+
+// One side's geometry: everything but the pointers of RsArgs.
+struct RsSide {
+    int k = 0, n = 0, n2 = 0, S = 0, blocks = 0, H = 0, D0 = 0, RB = 0, RS = 0, in_off = 0, out_row = 0;
+    bool relay = false;
+    int tpmax = 0;  // packets per chunk of a burst cut into several chunks (0: not even the smallest fits)
+};
+
+// LDS bytes of a launch whose chunks hold at most tp packets; fills the carve-up.
+size_t rs_lds(const RsSide& s, int tp, RsArgs* a) {
+    const int S4 = (s.S + 3) & ~3;
+    const size_t rows = static_cast<size_t>(s.H) + tp;
+    size_t off = align16(kRsOffTab + (s.relay ? static_cast<size_t>(s.n2 - s.k) * s.k * 20 : 0));
+    if (a) a->off_raw = static_cast<int>(off);
+    // the rows, with slack behind the last one for the CT build's reads past a row's last block;
+    // or the chunk's output rows at any byte phase
+    off = align16(off + std::max(rows * s.RS + 4 * s.n + 16, static_cast<size_t>(tp) * s.out_row + 4));
+    if (a) a->off_ct = static_cast<int>(off);
+    return align16(off + rows * s.k * S4);
+}
+
+// (T1, N1, T2, N2) as fec_swdf_create takes them, and n <= 17 (the window-n rule tables).
+bool rs_tuple_ok(int max_payload, int T1, int N1, int T2, int N2) {
+    if (max_payload < 1 || T1 < 0 || N1 < 0 || T2 < 1 || N2 < 0 || T1 - N1 != T2 - N2) return false;
+    const int k = T1 - N1 + 1;
+    return k >= 1 && k <= kMaxK && T1 + 1 <= kMaxRuleN && T2 + 1 <= kMaxRuleN;
+}
+
+RsSide rs_side(bool relay, int max_payload, int T1, int N1, int T2, int N2) {
+    RsSide s;
+    const int n1 = T1 + 1, n2 = T2 + 1;
+    s.relay = relay;
+    s.k = T1 - N1 + 1;
+    s.n = relay ? n1 : n2;
+    s.n2 = n2;
+    s.S = (max_payload + 2 + s.k - 1) / s.k;
+    s.blocks = std::min(s.S, max_payload / s.k + 1);
+    s.H = relay ? n1 + n2 - 2 : n2 - 1;
+    s.D0 = relay ? n2 - 1 : 0;
+    s.RB = s.S * s.n;
+    s.RS = 4 * ((s.RB + 6) >> 2);
+    s.in_off = relay ? 0 : 4;
+    s.out_row = relay ? 2 + (s.S + 1) * n2 : s.S * s.k;
+    // a burst of more than one chunk takes chunks of at least H packets (the rows in front of a
+    // later chunk all lie in the burst); the smallest chunk is one packet of a one-packet call
+    for (int tp = kRsTP; tp >= s.H && !s.tpmax; --tp)
+        if (rs_lds(s, tp, nullptr) <= static_cast<size_t>(kRsLds)) s.tpmax = tp;
+    return s;
+}
+
+// The flag half for one stream: the rows' window masks from the stream's flag register w (bit 63 =
+// the newest flag), which it advances.
+void rs_plan_rows(uint64_t* w, int n, const uint8_t* er, int64_t count, uint32_t* mask) {
+    for (int64_t t = 0; t < count; ++t) {
+        *w = (*w >> 1) | (static_cast<uint64_t>(er[t] != 0) << 63);
+        mask[t] = static_cast<uint32_t>(*w >> (64 - n));
+    }
+}
+
+}  // namespace
+}  // namespace fec
+
+struct fec_relay_streams {
+    struct Side {
+        fec::RsSide geo;
+        fec::CodecView v;
+        std::vector<int64_t> seq;    // seqs fed so far per stream
+        std::vector<uint64_t> hist;  // flags of the last 64 seqs per stream (bit 63 = the newest)
+        uint8_t* d_ring = nullptr;
+    };
+    fec_codec* hop1 = nullptr;
+    fec_codec* hop2 = nullptr;
+    Side relay, dest;
+    int nstreams = 0, F = 0;
+    uint32_t* d_tab = nullptr;               // gf_mul4x tables of G2's parity columns
+    std::vector<uint32_t> mark;              // duplicate-id check (call stamp per stream)
+    uint32_t stamp = 0;
+    std::vector<uint64_t> next_hist;         // a call's new flag registers, committed after the launch
+    // Per-call records (chunks + masks) go through a ring of pinned, mapped staging buffers that the
+    // kernels read in place (as fec_streams'): a buffer is rewritten only after the kernel that read it.
+    static constexpr int kStageBufs = 4;
+    void* h_stage[kStageBufs] = {};
+    void* m_stage[kStageBufs] = {};
+    size_t stage_cap[kStageBufs] = {};
+    hipEvent_t staged[kStageBufs] = {};
+    int buf = 0;
+    hipEvent_t done = nullptr;               // the last call's kernel (rings)
+    bool poisoned = false;                   // a failed call left host and device state apart
+    ~fec_relay_streams() {
+        for (hipEvent_t e : staged)
+            if (e) (void)hipEventDestroy(e);
+        if (done) (void)hipEventDestroy(done);
+        for (void* p : {static_cast<void*>(relay.d_ring), static_cast<void*>(dest.d_ring), static_cast<void*>(d_tab)})
+            if (p) (void)hipFree(p);
+        for (void* p : h_stage)
+            if (p) (void)hipHostFree(p);
+        if (hop1) fec_codec_destroy(hop1);
+        if (hop2) fec_codec_destroy(hop2);
+    }
+};
+
+namespace {
+
+int rs_stage_reserve(fec_relay_streams* h, int b, size_t bytes) {
+    if (bytes <= h->stage_cap[b]) return FEC_OK;
+    const size_t cap = std::max(bytes, 2 * h->stage_cap[b]);
+    if (h->h_stage[b]) FEC_HIP(hipHostFree(h->h_stage[b]));
+    h->h_stage[b] = nullptr;
+    h->m_stage[b] = nullptr;
+    h->stage_cap[b] = 0;
+    FEC_HIP(hipHostMalloc(&h->h_stage[b], cap, hipHostMallocMapped));
+    FEC_HIP(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
+    h->stage_cap[b] = cap;
+    return FEC_OK;
+}
+
+// A launch with more than 64 KB of dynamic LDS needs the kernel's limit raised first.
+int rs_lds_allow(const void* kernel, int lds, int* raised) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    if (lds <= 64 * 1024 || lds <= *raised) return FEC_OK;
+    FEC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    *raised = lds;
+    return FEC_OK;
+}
+
+// One side's call.  in: R rows of in_stride bytes; out: R rows of the side's out_row.
+template <bool RELAY>
+int rs_call(fec_relay_streams* h, fec_relay_streams::Side& sd, const int32_t* ids, const int32_t* counts, int M,
+            const uint8_t* erasure, const uint8_t* in, int64_t in_stride, uint8_t* out, uint8_t* flag, hipStream_t s) {
+    const fec::RsSide& g = sd.geo;
+    if (M < 0 || M > h->nstreams) return FEC_ERR_ARG;
+    if (M == 0) return FEC_OK;
+    if (!ids || !erasure || !in || !out || in_stride < g.in_off + g.RB) return FEC_ERR_ARG;
+    int64_t R = M;
+    int maxc = 1;
+    if (counts) {
+        R = 0;
+        for (int m = 0; m < M; ++m) {
+            if (counts[m] < 1) return FEC_ERR_ARG;
+            R += counts[m];
+            maxc = std::max(maxc, counts[m]);
+        }
+    }
+    if (++h->stamp == 0) {
+        std::fill(h->mark.begin(), h->mark.end(), 0u);
+        h->stamp = 1;
+    }
+    for (int m = 0; m < M; ++m) {
+        const int id = ids[m];
+        if (id < 0 || id >= h->nstreams || h->mark[id] == h->stamp) return FEC_ERR_ARG;
+        h->mark[id] = h->stamp;
+    }
+    // bursts of one chunk each when the longest fits a chunk; else chunks of tpmax >= H
+    fec::RsArgs a{};
+    int tp = maxc;
+    if (maxc > g.tpmax || fec::rs_lds(g, maxc, nullptr) > static_cast<size_t>(fec::kRsLds)) tp = g.tpmax;
+    const int lds = static_cast<int>(fec::rs_lds(g, tp, &a));
+    int64_t nu = 0;
+    for (int m = 0; m < M; ++m) nu += ((counts ? counts[m] : 1) + tp - 1) / tp;
+    if (nu > INT32_MAX) return FEC_ERR_ARG;
+    if (h->poisoned) return FEC_ERR_HIP;
+    // From here on a failure may leave the staging ring or the events in an unknown state.
+    struct Poison {
+        fec_relay_streams* h;
+        bool armed = true;
+        ~Poison() { if (armed) h->poisoned = true; }
+    } poison{h};
+    const void* kern = reinterpret_cast<const void*>(fec::fec_relay_streams_kernel<RELAY>);
+    static int lds_raised = 0;  // per kernel (this template instance), not per group
+    if (int st = rs_lds_allow(kern, lds, &lds_raised)) return st;
+    // This call's staging buffer is free once the call that used it last has run; the previous
+    // call's kernel (the rings' last reader and writer) comes before this one's on any stream.
+    const int b = h->buf;
+    FEC_HIP(hipEventSynchronize(h->staged[b]));
+    FEC_HIP(hipStreamWaitEvent(s, h->done, 0));
+    const size_t off_masks = fec::align16(static_cast<size_t>(nu) * sizeof(fec::RsUnit));
+    if (int st = rs_stage_reserve(h, b, off_masks + static_cast<size_t>(R) * 4)) return st;
+    fec::RsUnit* un = static_cast<fec::RsUnit*>(h->h_stage[b]);
+    uint32_t* masks = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(h->h_stage[b]) + off_masks);
+    int64_t row = 0;
+    for (int m = 0; m < M; ++m) {
+        const int id = ids[m], cnt = counts ? counts[m] : 1;
+        uint64_t w = sd.hist[id];
+        const uint32_t front = static_cast<uint32_t>(w >> (64 - g.H));  // bit i = flag of seq - H + i
+        fec::rs_plan_rows(&w, g.n, erasure + row, cnt, masks + row);
+        h->next_hist[m] = w;
+        for (int lead = 0; lead < cnt; lead += tp, ++un) {
+            un->row0 = row + lead;
+            un->seq0 = sd.seq[id] + lead;
+            un->id = id;
+            un->cnt = std::min(tp, cnt - lead);
+            un->lead = lead;
+            un->total = cnt;
+            un->hist = front;
+            un->pad = 0;
+        }
+        row += cnt;
+    }
+    const uint8_t* rec = static_cast<const uint8_t*>(h->m_stage[b]);
+    a.in = in;
+    a.in_stride = in_stride;
+    a.in_off = g.in_off;
+    a.units = reinterpret_cast<const fec::RsUnit*>(rec);
+    a.masks = reinterpret_cast<const uint32_t*>(rec + off_masks);
+    a.ring = sd.d_ring;
+    a.rules = sd.v.rules + sd.v.wbase_n;
+    a.gf = sd.v.gf;
+    a.tab = h->d_tab;
+    a.out = out;
+    a.flag = flag;
+    a.k = g.k, a.n = g.n, a.n2 = g.n2, a.S = g.S, a.S4 = (g.S + 3) & ~3, a.blocks = g.blocks, a.ES = sd.v.ES;
+    a.H = g.H, a.D0 = g.D0, a.RB = g.RB, a.RS = g.RS, a.out_row = g.out_row;
+    hipLaunchKernelGGL(fec::fec_relay_streams_kernel<RELAY>, dim3(static_cast<unsigned>(nu)), dim3(fec::kRsThreads),
+                       static_cast<size_t>(lds), s, a);
+    FEC_HIP(hipGetLastError());
+    FEC_HIP(hipEventRecord(h->done, s));
+    FEC_HIP(hipEventRecord(h->staged[b], s));
+    h->buf = (b + 1) % fec_relay_streams::kStageBufs;
+    for (int m = 0; m < M; ++m) {
+        sd.seq[ids[m]] += counts ? counts[m] : 1;
+        sd.hist[ids[m]] = h->next_hist[m];
+    }
+    poison.armed = false;
+    return FEC_OK;
+}
+
+int rs_create_side(fec_relay_streams::Side& sd, bool relay, const fec_codec* codec, int max_payload, int T1, int N1,
+                   int T2, int N2, int nstreams) {
+    sd.geo = fec::rs_side(relay, max_payload, T1, N1, T2, N2);
+    if (int st = fec::codec_view(codec, &sd.v)) return st;
+    if (sd.geo.tpmax == 0 || sd.v.wbase_n < 0 || sd.v.S != sd.geo.S || sd.v.n != sd.geo.n) return FEC_ERR_ARG;
+    sd.seq.assign(nstreams, 0);
+    sd.hist.assign(nstreams, 0);
+    const size_t rb = static_cast<size_t>(nstreams) * sd.geo.H * sd.geo.RB;
+    FEC_HIP(hipMalloc(&sd.d_ring, rb));
+    FEC_HIP(hipMemset(sd.d_ring, 0, rb));
+    return FEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fec_relay_streams_fit(int relay, int max_payload, int T1, int N1, int T2, int N2, int* chunk_packets,
+                          int* lds_bytes) {
+    if (!fec::rs_tuple_ok(max_payload, T1, N1, T2, N2)) return FEC_ERR_ARG;
+    const fec::RsSide s = fec::rs_side(relay != 0, max_payload, T1, N1, T2, N2);
+    if (chunk_packets) *chunk_packets = s.tpmax;
+    if (lds_bytes) *lds_bytes = s.tpmax ? static_cast<int>(fec::rs_lds(s, s.tpmax, nullptr)) : 0;
+    return s.tpmax ? 1 : 0;
+}
+
+int fec_relay_streams_plan_host(int k, int n, const uint8_t* erasure, const int32_t* counts, int ncounts,
+                                uint32_t* mask, uint8_t* flag) {
+    if (k < 1 || n < k || n > fec::kMaxN || !erasure || !counts || ncounts < 0 || !mask || !flag) return FEC_ERR_ARG;
+    for (int c = 0; c < ncounts; ++c)
+        if (counts[c] < 1) return FEC_ERR_ARG;
+    uint64_t w = 0;
+    int64_t seq = 0;
+    for (int c = 0; c < ncounts; ++c) {
+        fec::rs_plan_rows(&w, n, erasure + seq, counts[c], mask + seq);
+        for (int64_t t = seq; t < seq + counts[c]; ++t) flag[t] = __builtin_popcount(mask[t]) >= n - k + 1 ? 1 : 0;
+        seq += counts[c];
+    }
+    return FEC_OK;
+}
+
+int fec_relay_streams_create(int max_payload, int T1, int N1, int T2, int N2, int nstreams, fec_relay_streams** out) {
+    if (!out) return FEC_ERR_ARG;
+    *out = nullptr;
+    if (nstreams <= 0 || !fec::rs_tuple_ok(max_payload, T1, N1, T2, N2)) return FEC_ERR_ARG;
+    // a geometry whose smallest chunk does not fit a CU's LDS, before anything is allocated
+    if (!fec::rs_side(true, max_payload, T1, N1, T2, N2).tpmax || !fec::rs_side(false, max_payload, T1, N1, T2, N2).tpmax)
+        return FEC_ERR_ARG;
+    try {
+        std::unique_ptr<fec_relay_streams> h(new fec_relay_streams());
+        // the codecs of fec_swdf_create: Decoder(n-1, n-k, n-k) per hop
+        if (int st = fec_codec_create(max_payload, T1, N1, N1, &h->hop1)) return st;
+        if (int st = fec_codec_create(max_payload, T2, N2, N2, &h->hop2)) return st;
+        h->nstreams = nstreams;
+        if (int st = rs_create_side(h->relay, true, h->hop1, max_payload, T1, N1, T2, N2, nstreams)) return st;
+        if (int st = rs_create_side(h->dest, false, h->hop2, max_payload, T1, N1, T2, N2, nstreams)) return st;
+        h->F = h->relay.geo.out_row;
+        h->mark.assign(nstreams, 0);
+        h->next_hist.assign(nstreams, 0);
+        {
+            // gf_mul4x tables (fec_device.h) of G2[k-1-m][p], p >= k: c*{0..7}, c*({0..7}<<3), c*({0..3}<<6)
+            const int k = h->relay.geo.k, n2 = h->relay.geo.n2;
+            const std::vector<uint8_t> G2 = fec::make_generator(T2, N2, N2);
+            const fec::Field& f = fec::field();
+            std::vector<uint32_t> tab(static_cast<size_t>(std::max(1, (n2 - k) * k)) * 5, 0);
+            for (int p = k; p < n2; ++p)
+                for (int m = 0; m < k; ++m) {
+                    const uint8_t c = G2[(k - 1 - m) * n2 + p];
+                    uint32_t* t = &tab[(static_cast<size_t>(p - k) * k + m) * 5];
+                    for (int x = 0; x < 8; ++x) {
+                        t[x >> 2] |= uint32_t(f.mt[c][x]) << (8 * (x & 3));
+                        t[2 + (x >> 2)] |= uint32_t(f.mt[c][x << 3]) << (8 * (x & 3));
+                    }
+                    for (int x = 0; x < 4; ++x) t[4] |= uint32_t(f.mt[c][x << 6]) << (8 * x);
+                }
+            FEC_HIP(hipMalloc(&h->d_tab, tab.size() * 4));
+            FEC_HIP(hipMemcpy(h->d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        }
+        const size_t stage = static_cast<size_t>(nstreams) * (sizeof(fec::RsUnit) + 4) + 64;
+        for (int b = 0; b < fec_relay_streams::kStageBufs; ++b) {
+            if (int st = rs_stage_reserve(h.get(), b, stage)) return st;
+            FEC_HIP(hipEventCreateWithFlags(&h->staged[b], hipEventDisableTiming));
+            FEC_HIP(hipEventRecord(h->staged[b], nullptr));
+        }
+        FEC_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+        FEC_HIP(hipEventRecord(h->done, nullptr));
+        *out = h.release();
+        return FEC_OK;
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    } catch (...) {
+        return FEC_ERR_ARG;
+    }
+}
+
+int fec_relay_streams_destroy(fec_relay_streams* h) {
+    delete h;
+    return FEC_OK;
+}
+
+int fec_relay_streams_geometry(const fec_relay_streams* h, int* k, int* n1, int* n2, int* S, int* cw_bytes,
+                               int* frame_bytes, int* delay) {
+    if (!h) return FEC_ERR_ARG;
+    const fec::RsSide& r = h->relay.geo;
+    if (k) *k = r.k;
+    if (n1) *n1 = r.n;
+    if (n2) *n2 = r.n2;
+    if (S) *S = r.S;
+    if (cw_bytes) *cw_bytes = r.RB;
+    if (frame_bytes) *frame_bytes = h->F;
+    if (delay) *delay = r.n + r.n2 - r.k - 1;
+    return FEC_OK;
+}
+
+int fec_relay_streams_relay(fec_relay_streams* h, const int32_t* ids, const int32_t* counts, int M,
+                            const uint8_t* erasure, const uint8_t* d_cw, int64_t cw_stride, uint8_t* d_frames,
+                            uint8_t* d_flag, void* stream) {
+    if (!h) return FEC_ERR_ARG;
+    try {
+        return rs_call<true>(h, h->relay, ids, counts, M, erasure, d_cw, cw_stride, d_frames, d_flag,
+                             static_cast<hipStream_t>(stream));
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    }
+}
+
+int fec_relay_streams_destination(fec_relay_streams* h, const int32_t* ids, const int32_t* counts, int M,
+                                  const uint8_t* erasure, const uint8_t* d_frames, uint8_t* d_out, uint8_t* d_flag,
+                                  void* stream) {
+    if (!h) return FEC_ERR_ARG;
+    try {
+        return rs_call<false>(h, h->dest, ids, counts, M, erasure, d_frames, h->F, d_out, d_flag,
+                              static_cast<hipStream_t>(stream));
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    }
+}
+
+int fec_relay_streams_state(const fec_relay_streams* h, int id, int64_t* relayed, int64_t* delivered) {
+    if (!h || id < 0 || id >= h->nstreams) return FEC_ERR_ARG;
+    if (relayed) *relayed = h->relay.seq[id];
+    if (delivered) *delivered = h->dest.seq[id];
+    return FEC_OK;
+}
+
+}  // extern "C"

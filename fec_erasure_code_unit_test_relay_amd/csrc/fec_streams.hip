@@ -374,44 +374,6 @@ struct BurstDecArgs {
     FastDiv dk, dlw, dcwd;
 };
 
-// Global bytes g[0, nb) into LDS, byte j at smem[off + (g & 3) + j] (off a multiple of 4): whole
-// dwords with dword loads, the up to 3 + 3 bytes in front of and behind them with byte loads.
-__device__ __forceinline__ void burst_stage(uint8_t* smem, int off, const uint8_t* g, int nb, int t, int nt) {
-    const int a = static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
-    const int head = min(nb, (4 - a) & 3);
-    const int nd = (nb - head) >> 2;
-    const uint32_t* gd = reinterpret_cast<const uint32_t*>(g + head);
-    uint32_t* ld = reinterpret_cast<uint32_t*>(smem + off + ((a + head) & ~3));
-    if (((a + head) & 3) == 0) {
-#pragma unroll 4
-        for (int w = t; w < nd; w += nt) ld[w] = gd[w];
-    }
-    const int tail0 = head + 4 * nd;
-    if (t < head) smem[off + a + t] = g[t];
-    if (t < nb - tail0) smem[off + a + tail0 + t] = g[tail0 + t];
-}
-
-// LDS bytes smem[off, off + nb) to global g[0, nb): whole dwords with dword stores.
-__device__ __forceinline__ void burst_flush(uint8_t* g, const uint8_t* smem, int off, int nb, int t, int nt) {
-    const int a = static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
-    const int head = min(nb, (4 - a) & 3);
-    const int nd = (nb - head) >> 2;
-    const int tail0 = head + 4 * nd;
-    if (nd > 0) {  // then g + head is a dword address
-        uint32_t* gd = reinterpret_cast<uint32_t*>(g + head);
-        const uint8_t* s = smem + off + head;
-        if (((off + head) & 3) == 0) {
-            for (int w = t; w < nd; w += nt) gd[w] = reinterpret_cast<const uint32_t*>(s)[w];
-        } else {
-            for (int w = t; w < nd; w += nt)
-                gd[w] = uint32_t(s[4 * w]) | (uint32_t(s[4 * w + 1]) << 8) | (uint32_t(s[4 * w + 2]) << 16) |
-                        (uint32_t(s[4 * w + 3]) << 24);
-        }
-    }
-    if (t < head) g[t] = smem[off + t];
-    if (t < nb - tail0) g[tail0 + t] = smem[off + tail0 + t];
-}
-
 // One workgroup per chunk.  LDS: the parity tables; the windows of the chunk's packets and of the
 // n-1 in front of them as position planes [i][row][sub-stream] (the four sub-streams of one
 // gf_mul4x sit in one dword); the chunk's payload rows, later its codewords; the ring's rows.

@@ -84,6 +84,127 @@ class SymbolWiseRelay:
         return out, flag
 
 
+class RelayStreamGroup:
+    """``nstreams`` independent SWDF chains of one (max_payload, T1, N1, T2, N2) (fec_relay_streams_*):
+    one Decoder_Symbol_Wise per stream and side, its state on the device between calls.  Each call
+    hands over the next packet, or the next ``counts[m]`` packets, of every listed stream in one
+    launch; per stream the rows of all calls together are SymbolWiseRelay.relay / .destination over
+    the stream's whole sequence.  A relay node uses ``relay``, a destination node ``destination``."""
+
+    def __init__(self, max_payload: int, T1: int, N1: int, T2: int, N2: int, nstreams: int):
+        h = ctypes.c_void_p()
+        check(lib().fec_relay_streams_create(max_payload, T1, N1, T2, N2, nstreams, ctypes.byref(h)),
+              "fec_relay_streams_create")
+        self._h = h
+        v = [ctypes.c_int() for _ in range(7)]
+        check(lib().fec_relay_streams_geometry(h, *[ctypes.byref(x) for x in v]), "fec_relay_streams_geometry")
+        self.k, self.n1, self.n2, self.S, self.cw_bytes, self.frame_bytes, self.delay = (x.value for x in v)
+        self.L, self.nstreams = max_payload, nstreams
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().fec_relay_streams_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+    @staticmethod
+    def _rows(ids, counts, erasure):
+        """Host arrays of a call: ids int32 [M], counts int32 [M] or None (one packet of each), the
+        R = sum(counts) flags.  A count < 1 is the library's to refuse; it adds no rows here."""
+        import numpy as np
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        assert ids.ndim == 1
+        if counts is None:
+            R = ids.size
+        else:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            assert counts.shape == ids.shape
+            R = int(np.maximum(counts, 0).sum(dtype=np.int64))
+        er = np.ascontiguousarray(erasure, dtype=np.uint8)
+        assert er.size == R
+        return ids, counts, er, R
+
+    @staticmethod
+    def _host(a):
+        return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+
+    def relay(self, ids, counts, erasure, codewords, frames=None, flag=None):
+        """symbol_wise_encode_1 for the next counts[m] seqs of stream ids[m]: codewords [R, >=
+        cw_bytes] uint8 on the GPU (rows as in StreamGroup.encode_burst: stream ids[m]'s from row
+        sum(counts[:m]) on; any row stride, any alignment; rows of erased packets are never read),
+        erasure R host flags -> (frames [R, frame_bytes], flags [R] uint8) on the GPU."""
+        import torch
+        ids, counts, er, R = self._rows(ids, counts, erasure)
+        assert codewords.dtype == torch.uint8 and codewords.is_cuda and codewords.dim() == 2
+        assert codewords.shape[0] == R and codewords.shape[1] >= self.cw_bytes
+        assert R == 0 or codewords.stride(1) == 1
+        if frames is None:
+            frames = torch.empty((R, self.frame_bytes), dtype=torch.uint8, device=codewords.device)
+        assert frames.shape == (R, self.frame_bytes) and frames.is_contiguous() and frames.dtype == torch.uint8
+        if flag is None:
+            flag = torch.empty(R, dtype=torch.uint8, device=codewords.device)
+        assert flag.numel() >= R and flag.dtype == torch.uint8 and flag.is_contiguous()
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(lib().fec_relay_streams_relay(self._h, self._host(ids), self._host(counts), ids.size, self._host(er),
+                                            _ptr(codewords), codewords.stride(0) if R else self.cw_bytes,
+                                            _ptr(frames), _ptr(flag), stream), "fec_relay_streams_relay")
+        return frames, flag
+
+    def destination(self, ids, counts, erasure, frames, out=None, flag=None):
+        """symbol_wise_decode_1 + extract_data for the next counts[m] seqs of stream ids[m]: frames
+        [R, frame_bytes] on the GPU, erasure R host flags -> (data_with_header rows [R, S*k] (a row
+        = source packet seq - delay of its stream), flags [R] uint8) on the GPU."""
+        import torch
+        ids, counts, er, R = self._rows(ids, counts, erasure)
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
+        assert tuple(frames.shape) == (R, self.frame_bytes)
+        if out is None:
+            out = torch.empty((R, self.S * self.k), dtype=torch.uint8, device=frames.device)
+        assert out.shape == (R, self.S * self.k) and out.is_contiguous() and out.dtype == torch.uint8
+        if flag is None:
+            flag = torch.empty(R, dtype=torch.uint8, device=frames.device)
+        assert flag.numel() >= R and flag.dtype == torch.uint8 and flag.is_contiguous()
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(lib().fec_relay_streams_destination(self._h, self._host(ids), self._host(counts), ids.size,
+                                                  self._host(er), _ptr(frames), _ptr(out), _ptr(flag), stream),
+              "fec_relay_streams_destination")
+        return out, flag
+
+    def state(self, stream_id: int):
+        """(seqs relayed, seqs delivered) of one stream."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        check(lib().fec_relay_streams_state(self._h, stream_id, ctypes.byref(a), ctypes.byref(b)),
+              "fec_relay_streams_state")
+        return a.value, b.value
+
+
+def relay_streams_fit(relay: bool, max_payload: int, T1: int, N1: int, T2: int, N2: int):
+    """Host only: whether one side of a relay stream group fits a CU's LDS -> (fits, packets per chunk
+    of a long burst, that chunk's LDS bytes); FecError for a tuple the group refuses."""
+    tp, lds = ctypes.c_int(), ctypes.c_int()
+    st = lib().fec_relay_streams_fit(int(relay), max_payload, T1, N1, T2, N2, ctypes.byref(tp), ctypes.byref(lds))
+    if st < 0:
+        check(st, "fec_relay_streams_fit")
+    return bool(st), tp.value, lds.value
+
+
+def relay_streams_plan_host(k: int, n: int, erasure, counts):
+    """Host only: the flag half of one side for one stream from seq 0 fed in bursts of ``counts`` ->
+    (window mask per row [P] uint32, loss flag per row [P] uint8)."""
+    import numpy as np
+    e = np.ascontiguousarray(erasure, dtype=np.uint8)
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    assert int(np.maximum(c, 0).sum(dtype=np.int64)) == e.size
+    mask = np.zeros(e.size, dtype=np.uint32)
+    flag = np.zeros(e.size, dtype=np.uint8)
+    check(lib().fec_relay_streams_plan_host(k, n, e.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p),
+                                            c.size, mask.ctypes.data_as(ctypes.c_void_p),
+                                            flag.ctypes.data_as(ctypes.c_void_p)), "fec_relay_streams_plan_host")
+    return mask, flag
+
+
 class StateDependentRelay:
     """Fixed-rate SD-SWDF chain (RELAYING_TYPE 3): source (T1, N1, N1) -> relay
     (symbol_wise_encode_state_dependent, Decoder_Symbol_Wise.cpp:178-432) -> destination

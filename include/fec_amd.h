@@ -372,6 +372,57 @@ int fec_swdf_relay_batch(fec_swdf *swdf, const uint8_t *d_cw, int64_t cw_stride,
 int fec_swdf_destination_batch(fec_swdf *swdf, const uint8_t *d_frames, const uint8_t *d_erasure, int64_t P,
                                uint8_t *d_out, uint8_t *d_flag, void *hip_stream);
 
+/* ---- relay stream groups: SWDF for many relay streams per launch ------------------------------
+ * nstreams independent type-2 relay chains of one (max_payload, T1, N1, T2, N2) (the constraints of
+ * fec_swdf_create, and n1, n2 <= 17: the window-n rule tables), each stream's state on the device
+ * between calls: one Decoder_Symbol_Wise per stream and side, fed one packet or a burst per call.
+ * A relay node uses the relay side, a destination node the destination side of one group.
+ *   fec_relay_streams_relay = push_current_codeword / rotate_pointers_and_insert_zero_word +
+ *     symbol_wise_encode_1 (src/Decoder_Symbol_Wise.cpp:119-176, :547-619, driven by
+ *     Variable_Rate_FEC_Decoder.cpp:950-1601) for the next counts[m] seqs of stream ids[m];
+ *   fec_relay_streams_destination = the same window over the relay's frames + symbol_wise_decode_1 +
+ *     extract_data (:621-665, driven by Variable_Rate_FEC_Decoder.cpp:1603-1879).
+ * Rows: ids M distinct stream ids (host); counts M burst sizes >= 1 (host; NULL: one packet of
+ * each); with R = the sum of the counts every row array has R rows, stream ids[m]'s from row
+ * counts[0] + .. + counts[m-1] on, its next counts[m] seqs in order (the layout of
+ * fec_streams_encode_burst; R is not bounded by nstreams).  erasure: R host flags.  d_cw: R rows of
+ * cw_stride >= S*n1 bytes (rows of erased packets are never read); d_frames: R rows of frame_bytes;
+ * d_out: R rows of S*k bytes (data_with_header of source packet seq - delay); d_flag: R bytes (may be
+ * NULL), 1 when the row's window held n-k+1 or more erasures.  Per stream, the rows of all calls
+ * together equal fec_swdf_relay_batch / fec_swdf_destination_batch over the stream's whole sequence
+ * from seq 0, row for row; one-packet calls and bursts continue each other.
+ * No pointer or row needs any alignment (frame rows are 431 bytes at (10,3,10,3)).
+ * Calls on different HIP streams are ordered by the group.  FEC_ERR_ARG (a repeated or out-of-range
+ * id, a count < 1, a null pointer, cw_stride < S*n1; at create a geometry whose smallest chunk does
+ * not fit a CU's LDS) leaves the group unchanged; any later failure poisons it (every further call
+ * returns FEC_ERR_HIP). */
+typedef struct fec_relay_streams fec_relay_streams;
+int fec_relay_streams_create(int max_payload, int T1, int N1, int T2, int N2, int nstreams,
+                             fec_relay_streams **out);
+int fec_relay_streams_destroy(fec_relay_streams *group);
+/* cw_bytes = S*n1; delay = n1 + n2 - k - 1 (fec_swdf_geometry) */
+int fec_relay_streams_geometry(const fec_relay_streams *group, int *k, int *n1, int *n2, int *S, int *cw_bytes,
+                               int *frame_bytes, int *delay);
+int fec_relay_streams_relay(fec_relay_streams *group, const int32_t *ids, const int32_t *counts, int M,
+                            const uint8_t *erasure, const uint8_t *d_cw, int64_t cw_stride, uint8_t *d_frames,
+                            uint8_t *d_flag, void *hip_stream);
+int fec_relay_streams_destination(fec_relay_streams *group, const int32_t *ids, const int32_t *counts, int M,
+                                  const uint8_t *erasure, const uint8_t *d_frames, uint8_t *d_out,
+                                  uint8_t *d_flag, void *hip_stream);
+/* seqs stream id has been fed so far on the relay / the destination side */
+int fec_relay_streams_state(const fec_relay_streams *group, int id, int64_t *relayed, int64_t *delivered);
+/* Host only, no device call.  fit: whether a side (relay != 0: the relay's) of this geometry fits a
+ * CU's LDS: 1 with the packets per chunk of long bursts and that chunk's LDS bytes, 0 if not even the
+ * smallest chunk fits, FEC_ERR_ARG for a tuple fec_relay_streams_create refuses.
+ * plan_host: the flag half of a side for one stream from seq 0 fed in bursts of counts[]: per row the
+ * n-bit window mask (bit m = flag of seq t-n+1+m, zero before seq 0: the index of the codec's
+ * window-n decode rule, decodeBlock(T = n-1, t = 0), Decoder_Symbol_Wise.cpp:570-573, :640-643) and
+ * the loss flag popcount(mask) >= n-k+1. */
+int fec_relay_streams_fit(int relay, int max_payload, int T1, int N1, int T2, int N2, int *chunk_packets,
+                          int *lds_bytes);
+int fec_relay_streams_plan_host(int k, int n, const uint8_t *erasure, const int32_t *counts, int ncounts,
+                                uint32_t *mask, uint8_t *flag);
+
 /* ---- relay: state-dependent symbol-wise decode-and-forward (SD-SWDF, RELAYING_TYPE 3) --------
  * Decoder_Symbol_Wise::symbol_wise_encode_state_dependent (src/Decoder_Symbol_Wise.cpp:178-432) at
  * the relay and symbol_wise_decode_state_dependent + extract_data (:487-546, :653-661) at the
