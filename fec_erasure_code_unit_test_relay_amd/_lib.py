@@ -89,6 +89,11 @@ def lib() -> ctypes.CDLL:
     L.fec_streams_encode_burst.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.fec_streams_decode_burst.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.fec_streams_plan_burst_host.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp]
+    L.fec_streams_create_mixed.argtypes = [i32, vp, i32, vp, i32, ctypes.POINTER(vp)]
+    L.fec_streams_codes.argtypes = [vp, ip, ip]
+    L.fec_streams_stream_geometry.argtypes = [vp, i32, ip, ip, ip, ip, ip, ip]
+    L.fec_streams_set_code.argtypes = [vp, i32, i32]
+    L.fec_streams_mixed_fit.argtypes = [i32, vp, i32, vp, vp, vp, vp]
     L.fec_decode_stream_create.argtypes = [ctypes.POINTER(vp)]
     L.fec_decode_stream_destroy.argtypes = [vp]
     L.fec_decode_stream_state.argtypes = [vp, i64p, i64p]
@@ -182,7 +187,9 @@ def lib() -> ctypes.CDLL:
                  "fec_decode_stream_create", "fec_decode_stream_destroy", "fec_decode_stream_state",
                  "fec_decode_stream_push", "fec_streams_create", "fec_streams_destroy", "fec_streams_encode",
                  "fec_streams_decode", "fec_streams_state", "fec_streams_encode_burst",
-                 "fec_streams_decode_burst", "fec_streams_plan_burst_host",
+                 "fec_streams_decode_burst", "fec_streams_plan_burst_host", "fec_streams_create_mixed",
+                 "fec_streams_codes", "fec_streams_stream_geometry", "fec_streams_set_code",
+                 "fec_streams_mixed_fit",
                  "fec_decode_apply", "fec_decode_copy", "fec_decode_recover",
                  "fec_decode_counters", "fec_decode_plan_stats", "fec_timing_enable", "fec_timing_collect",
                  "fec_encoder_create", "fec_encoder_destroy", "fec_encoder_transmit",

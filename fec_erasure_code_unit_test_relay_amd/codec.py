@@ -325,6 +325,45 @@ class StreamGroup:
         self.n = self.k + B
         self.S = -(-(max_payload + 2) // self.k)
         self.CW = self.S * self.n
+        self.codes = [(T, B, N)]
+        self.code_of = np.zeros(nstreams, dtype=np.int32)
+
+    @classmethod
+    def mixed(cls, max_payload: int, tuples, code_of) -> "StreamGroup":
+        """A group whose stream s runs code tuples[code_of[s]] = (T,B,N) (fec_streams_create_mixed):
+        one call codes streams of different codes in one launch.  Codeword rows have one stride,
+        CW = the largest CW of the codes; a stream's codeword is the first geometry(s)["CW"] bytes
+        of its row and the rest is zero.  T, k, n and S are None: they are per stream."""
+        tup = np.ascontiguousarray(tuples, dtype=np.int32).reshape(-1, 3)
+        cof = np.ascontiguousarray(code_of, dtype=np.int32).reshape(-1)
+        h = ctypes.c_void_p()
+        check(lib().fec_streams_create_mixed(max_payload, tup.ctypes.data_as(ctypes.c_void_p), tup.shape[0],
+                                             cof.ctypes.data_as(ctypes.c_void_p), cof.size, ctypes.byref(h)),
+              "fec_streams_create_mixed")
+        self = cls.__new__(cls)
+        self._h = h
+        self.L, self.nstreams = max_payload, cof.size
+        self.T = self.k = self.n = self.S = None
+        nc, cws = ctypes.c_int(), ctypes.c_int()
+        check(lib().fec_streams_codes(h, ctypes.byref(nc), ctypes.byref(cws)), "fec_streams_codes")
+        assert nc.value == tup.shape[0]
+        self.CW = cws.value
+        self.codes = [tuple(int(v) for v in t) for t in tup]
+        self.code_of = np.array([self.geometry(s)["code"] for s in range(cof.size)], dtype=np.int32)
+        return self
+
+    def geometry(self, stream_id: int) -> dict:
+        """Stream `stream_id`'s code index and that code's T, k, n, S and CW."""
+        v = [ctypes.c_int() for _ in range(6)]
+        check(lib().fec_streams_stream_geometry(self._h, stream_id, *[ctypes.byref(x) for x in v]),
+              "fec_streams_stream_geometry")
+        return dict(zip(("code", "T", "k", "n", "S", "CW"), (x.value for x in v)))
+
+    def set_code(self, stream_id: int, code: int) -> None:
+        """Stream `stream_id` becomes a fresh encoder and decoder of code `code` (seq counters 0);
+        the old code's last T packets are never output."""
+        check(lib().fec_streams_set_code(self._h, stream_id, code), "fec_streams_set_code")
+        self.code_of[stream_id] = code
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -485,6 +524,17 @@ def plan_host(max_payload: int, T: int, B: int, N: int, erasure: np.ndarray) -> 
     check(lib().fec_plan_host(max_payload, T, B, N, e.ctypes.data_as(ctypes.c_void_p), e.size,
                               fate.ctypes.data_as(ctypes.c_void_p)), "fec_plan_host")
     return fate[: max(0, e.size - T)]
+
+
+def streams_mixed_fit(max_payload: int, tuples):
+    """Host only: per code of a mixed stream group (enc chunk, enc LDS bytes, dec chunk, dec LDS bytes)
+    as int32 arrays [ncodes] (fec_streams_mixed_fit); raises FecError if a tuple is refused or does not fit."""
+    tup = None if tuples is None else np.ascontiguousarray(tuples, dtype=np.int32).reshape(-1, 3)
+    nc = 0 if tup is None else tup.shape[0]
+    res = [np.zeros(max(nc, 1), dtype=np.int32) for _ in range(4)]
+    check(lib().fec_streams_mixed_fit(max_payload, None if tup is None else tup.ctypes.data_as(ctypes.c_void_p), nc,
+                                      *[r.ctypes.data_as(ctypes.c_void_p) for r in res]), "fec_streams_mixed_fit")
+    return tuple(r[:nc] for r in res)
 
 
 def plan_burst_host(max_payload: int, T: int, B: int, N: int, erasure: np.ndarray, counts) -> np.ndarray:

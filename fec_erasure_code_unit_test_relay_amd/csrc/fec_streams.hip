@@ -16,6 +16,8 @@
 // A burst call (fec_streams_encode_burst / fec_streams_decode_burst) hands over several consecutive
 // packets of each stream and equals that many one-packet calls; its kernels work on chunks of a
 // burst and touch the per-stream state only at the burst's two ends (see "bursts" below).
+// A mixed group (fec_streams_create_mixed) gives every stream its own (T,B,N): its calls run the burst
+// kernels' chunks with each chunk's geometry taken from a per-code table (see "mixed groups" below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -669,6 +671,379 @@ __global__ __launch_bounds__(256) void fec_streams_decode_burst_kernel(BurstDecA
     }
 }
 
+// ---- mixed groups: a code per stream, every chunk with its own geometry ------------------------
+// The burst kernels' work with the geometry taken from a per-code table in device memory instead of
+// the kernel arguments: a chunk's unit names its code, and since the code is the same for the whole
+// workgroup (read through readfirstlane) the table entry arrives by scalar loads, once, before the
+// kernel's first store.  The group's rows and slots have one stride for all codes: codeword rows
+// cwr = the largest CW (a stream's codeword is the first CW bytes of its row, its own code's CW;
+// encode zeroes the rest, decode never reads it), a window slot of `slot` bytes and a ring slot of
+// kRR x cwr bytes per stream, in which a stream uses its own W, SK and CW.
+// A stream that changes code (fec_streams_set_code) starts again at seq 0 in the same slots with
+// nothing cleared: both kernels read a window / ring row only for a packet seq >= 0 of the stream's
+// current life (the `u.seq0 + p >= 0` tests below), and every such window row was written in this
+// life; a ring row of a missing packet keeps older bytes, which meet only zero coefficients, as in
+// the burst kernels.
+
+struct MixedUnit {   // one chunk = one workgroup
+    int64_t row0;    // its first row in the call's row arrays
+    int64_t seq0;    // that row's sequence number in its stream
+    int64_t coef;    // decode: byte offset of the chunk's first coefficient block (k x n of its own code each)
+    int32_t id;
+    int32_t cnt;     // rows of the chunk (<= the code's TP)
+    int32_t lead;    // rows of the burst in front of the chunk (0: the first chunk)
+    int32_t total;   // rows of the burst
+    int32_t code;
+    int32_t pad;
+};
+
+struct MixedEncCode {  // table entry of one code
+    BurstEncArgs g;    // burst_enc_lds' geometry at the code's chunk size, and ptab (no other pointer is used)
+    int64_t slot;      // bytes of a stream's window slot
+    int cwr;           // the group's codeword row stride
+    int pad;
+};
+struct MixedDecCode {
+    BurstDecArgs g;    // burst_dec_lds' geometry at the code's chunk size, and gf
+    int cwr;
+    int pad;
+};
+
+struct MixedEncArgs {
+    const uint8_t* payload;  // R rows of L bytes
+    const int32_t* len;      // R payload sizes (null: all L)
+    const MixedUnit* units;
+    const MixedEncCode* codes;
+    uint8_t* win;            // [streams][slot]
+    uint8_t* cw;             // R rows of cwr bytes
+    int32_t* cw_len;
+};
+
+struct MixedDecArgs {
+    const uint8_t* cw_in;    // R rows of cwr bytes (rows of erased packets are not read)
+    const MixedUnit* units;
+    const MixedDecCode* codes;
+    const uint8_t* flags;    // R bytes: fate | kRowClamp | kRowErased
+    const uint8_t* coefs;    // the recovered rows' k x n blocks
+    uint8_t* ring;           // [streams][kRR][cwr]
+    uint8_t* out;            // R rows of L bytes
+    int32_t* out_len;
+};
+
+// Zero global g[0, nb): whole dwords with dword stores.
+__device__ __forceinline__ void burst_zero(uint8_t* g, int nb, int t, int nt) {
+    const int a = static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
+    const int head = min(nb, (4 - a) & 3);
+    const int nd = (nb - head) >> 2;
+    const int tail0 = head + 4 * nd;
+    uint32_t* gd = reinterpret_cast<uint32_t*>(g + head);
+    for (int w = t; w < nd; w += nt) gd[w] = 0;
+    if (t < head) g[t] = 0;
+    if (t < nb - tail0) g[tail0 + t] = 0;
+}
+
+// fec_streams_encode_burst_kernel's chunk, its geometry from the table.
+__global__ __launch_bounds__(256) void fec_streams_encode_mixed_kernel(MixedEncArgs a) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    const int tid = threadIdx.x;
+    const MixedUnit u = a.units[blockIdx.x];
+    const MixedEncCode c = a.codes[__builtin_amdgcn_readfirstlane(u.code)];
+    const BurstEncArgs& g = c.g;
+    const int L = g.L, k = g.k, n = g.n, S = g.S, SP = g.SP, NS4 = g.NS4, CW = g.CW, SK = g.SK, SKS = g.SKS;
+    const int W = g.W, ROWS = g.ROWS, np = n - k, H = n - 1, CWR = c.cwr;
+    uint32_t* tab = reinterpret_cast<uint32_t*>(smem);
+    uint8_t* planes = smem + g.off_planes;
+    int* lens = reinterpret_cast<int*>(smem + g.off_len);  // per row: payload size; -1 no packet; -2 ring row
+    for (int i = tid; i < k * np * 8; i += 256) tab[i] = g.ptab[i];
+    const int hb = min(H, u.lead);  // rows in front of the chunk that lie in the burst
+    uint8_t* slot = a.win + static_cast<int64_t>(u.id) * c.slot;
+    // row r = packet seq0 + r - H; a ring row only for a packet of the stream's current life (seq >= 0)
+    for (int r = tid; r < ROWS; r += 256) {
+        const int p = r - H;
+        int v = -1;
+        if (p < u.cnt) {
+            if (p >= -hb)
+                v = a.len ? min(max(a.len[u.row0 + p], 0), L) : L;
+            else if (u.seq0 + p >= 0)
+                v = -2;
+        }
+        lens[r] = v;
+    }
+    const uint8_t* g0 = a.payload + (u.row0 - hb) * L;
+    burst_stage(smem, g.off_io, g0, (hb + u.cnt) * L, tid, 256);
+    for (int r = 0; r < H - hb; ++r) {  // ring rows (first chunk only)
+        const int64_t seq = u.seq0 + r - H;
+        if (seq >= 0) burst_stage(smem, g.off_ring + r * SKS, slot + (seq % W) * SK, SK, tid, 256);
+    }
+    __syncthreads();
+    // payload byte b of row r at smem[rawoff + r * L + b]
+    const int rawoff = g.off_io + static_cast<int>(reinterpret_cast<uintptr_t>(g0) & 3) - (H - hb) * L;
+    const int nq = (SK + 3) >> 2;
+    const FastDiv dnq = g.dnq;
+    auto lds_word = [&](int off) -> uint32_t {  // the dword at any LDS byte offset: two aligned reads
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(smem + (off & ~3));
+        return __builtin_amdgcn_alignbyte(w[1], w[0], off & 3);
+    };
+    for (int idx = tid; idx < ROWS * nq; idx += 256) {  // window bytes 4q .. 4q+3 of row r
+        const int r = fdiv(dnq, idx), q = idx - r * nq;
+        const int ln = lens[r];
+        uint32_t w = 0;  // [len_hi, len_lo, payload, zero pad] (Encoder.cpp:75-83)
+        if (ln >= 0) {
+            w = lds_word(rawoff + r * L + 4 * q - 2) & keep_bytes(ln + 2 - 4 * q);
+            if (q == 0) w = (w & 0xffff0000u) | static_cast<uint32_t>(ln >> 8) | (static_cast<uint32_t>(ln & 0xff) << 8);
+        } else if (ln == -2) {
+            const uint8_t* gr = slot + ((u.seq0 + r - H) % W) * SK;
+            w = lds_word(g.off_ring + r * SKS + static_cast<int>(reinterpret_cast<uintptr_t>(gr) & 3) + 4 * q);
+        }
+        int s = fdiv(g.dk, 4 * q), i = 4 * q - s * k;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * q + e < SK) planes[(i * ROWS + r) * SP + s] = static_cast<uint8_t>(w >> (8 * e));
+            if (++i == k) i = 0, ++s;
+        }
+    }
+    __syncthreads();  // the planes are complete; the payload rows give way to the codewords
+    uint8_t* gcw = a.cw + u.row0 * CWR;
+    const int ao = g.off_io + static_cast<int>(reinterpret_cast<uintptr_t>(gcw) & 3);
+    uint8_t* out = smem + ao;  // the chunk's codewords, packed at CW
+    for (int idx = tid; idx < u.cnt * nq; idx += 256) {  // systematic bytes
+        const int p = fdiv(dnq, idx), q = idx - p * nq;
+        int s = fdiv(g.dk, 4 * q), i = 4 * q - s * k;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * q + e < SK) out[p * CW + s * n + i] = planes[(i * ROWS + p + H) * SP + s];
+            if (++i == k) i = 0, ++s;
+        }
+    }
+    // parity column j of four sub-streams: XOR_i G[i][j] * X_{t-(j-i)}[s][i]; rows without a packet are zero
+    for (int jj = 0; jj < np; ++jj) {
+        const int j = k + jj;
+        for (int it = tid; it < u.cnt * NS4; it += 256) {
+            const int p = fdiv(g.dns4, it), gq = it - p * NS4;
+            uint32_t acc = 0;
+            for (int i = 0; i < k; ++i) {
+                const uint32_t* t = tab + (i * np + jj) * 8;
+                if (!t[5]) continue;
+                const int r = p + H - (j - i);
+                acc ^= gf_mul4x(t, *reinterpret_cast<const uint32_t*>(planes + (i * ROWS + r) * SP + 4 * gq));
+            }
+            uint8_t* o = out + p * CW + 4 * gq * n + j;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * gq + e < S) o[e * n] = static_cast<uint8_t>(acc >> (8 * e));
+        }
+    }
+    __syncthreads();
+    if (tid < u.cnt) a.cw_len[u.row0 + tid] = last_nonzero_end(out + tid * CW, CW);  // FEC_Encoder.cpp:55-60
+    if (CWR == CW) {
+        burst_flush(gcw, smem, ao, u.cnt * CW, tid, 256);
+    } else {  // a wave per row: the codeword, then zeros up to the group's stride
+        for (int p = tid >> 6; p < u.cnt; p += 4) {
+            burst_flush(gcw + p * CWR, smem, ao + p * CW, CW, tid & 63, 64);
+            burst_zero(gcw + p * CWR + CW, CWR - CW, tid & 63, 64);
+        }
+    }
+    if (u.lead != 0) return;
+    // the burst's last min(total, W) windows into the stream's slot
+    const int m = min(u.total, W), t0 = u.total - m;
+    const bool far = u.total > u.cnt;  // they lie (partly) behind this chunk: their payload rows again
+    const uint8_t* g1 = a.payload + (u.row0 + t0) * L;
+    const int raw1 = g.off_io + static_cast<int>(reinterpret_cast<uintptr_t>(g1) & 3);
+    if (far) {
+        __syncthreads();
+        burst_stage(smem, g.off_io, g1, m * L, tid, 256);
+        __syncthreads();
+    }
+    for (int idx = tid; idx < m * nq; idx += 256) {
+        const int tt = fdiv(dnq, idx), q = idx - tt * nq, t = t0 + tt;
+        const int ln = far ? (a.len ? min(max(a.len[u.row0 + t], 0), L) : L) : 0;
+        uint8_t v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int b = min(4 * q + e, SK - 1);
+            if (far) {
+                v[e] = b == 0 ? static_cast<uint8_t>(ln >> 8)
+                              : b == 1 ? static_cast<uint8_t>(ln & 0xff) : (b - 2 < ln ? smem[raw1 + tt * L + b - 2] : 0);
+            } else {
+                const int s = fdiv(g.dk, b), i = b - s * k;
+                v[e] = planes[(i * ROWS + t + H) * SP + s];
+            }
+        }
+        uint8_t* dst = slot + ((u.seq0 + t) % W) * SK + 4 * q;  // slot: a multiple of 16 bytes
+        if ((SK & 3) == 0) {
+            *reinterpret_cast<uint32_t*>(dst) = uint32_t(v[0]) | (uint32_t(v[1]) << 8) | (uint32_t(v[2]) << 16) |
+                                                (uint32_t(v[3]) << 24);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * q + e < SK) dst[e] = v[e];
+        }
+    }
+}
+
+// fec_streams_decode_burst_kernel's chunk, its geometry from the table.
+__global__ __launch_bounds__(256) void fec_streams_decode_mixed_kernel(MixedDecArgs a) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    const int tid = threadIdx.x;
+    const MixedUnit u = a.units[blockIdx.x];
+    const MixedDecCode c = a.codes[__builtin_amdgcn_readfirstlane(u.code)];
+    const BurstDecArgs& g = c.g;
+    const int L = g.L, k = g.k, n = g.n, CW = g.CW, CWS = g.CWS, CWD = g.CWD, LW = g.LW, T = g.T;
+    const int HR = g.HR, ROWS = g.ROWS, TP = g.TP, kn = k * n, CWR = c.cwr;
+    uint8_t* gexp = smem;
+    uint8_t* glog = smem + 512;
+    int* rowoff = reinterpret_cast<int*>(smem + g.off_meta);  // [ROWS] LDS offset of the row's byte 0; -1: none
+    int* cord = rowoff + ROWS;                                // [TP] coefficient block of a recovered row
+    int* lnS = cord + TP;                                     // [TP] output length
+    int* cpS = lnS + TP;                                      // [TP] payload bytes copied
+    uint8_t* fl = reinterpret_cast<uint8_t*>(cpS + TP);       // [TP] row flags
+    for (int i = tid; i < 768; i += 256) smem[i] = g.gf[i];
+    const int hb = min(HR, u.lead);
+    uint8_t* ringb = a.ring + static_cast<int64_t>(u.id) * kRR * CWR;
+    // row r = packet seq0 + r - HR; its codeword's address (null: missing, or before the stream's
+    // current life: a ring row is read only for seq >= 0)
+    for (int r = tid; r < ROWS; r += 256) {
+        const int p = r - HR;
+        const uint8_t* gr = nullptr;
+        if (p < u.cnt) {
+            if (p >= -hb) {
+                const uint8_t f = a.flags[u.row0 + p];
+                if (p >= 0) fl[p] = f;
+                if (!(f & kRowErased)) gr = a.cw_in + (u.row0 + p) * CWR;
+            } else if (u.seq0 + p >= 0) {
+                gr = ringb + ((u.seq0 + p) % kRR) * CWR;
+            }
+        }
+        rowoff[r] = gr ? g.off_rows + r * CWS + static_cast<int>(reinterpret_cast<uintptr_t>(gr) & 3) : -1;
+    }
+    __syncthreads();
+    auto row_src = [&](int r) -> const uint8_t* {
+        if (rowoff[r] < 0) return nullptr;
+        const int p = r - HR;
+        return p >= -hb ? a.cw_in + (u.row0 + p) * CWR : ringb + ((u.seq0 + p) % kRR) * CWR;
+    };
+    if (tid < u.cnt) {
+        int cnt = 0;
+        for (int j = 0; j < tid; ++j) cnt += (fl[j] & 3) == kRecovered;
+        cord[tid] = cnt;
+    }
+    int nrec = 0;
+    for (int j = 0; j < u.cnt; ++j) nrec += (fl[j] & 3) == kRecovered;
+    const uint8_t* gco = a.coefs + u.coef;
+    if (nrec) burst_stage(smem, g.off_coef, gco, nrec * kn, tid, 256);
+    const uint8_t* coefs = smem + g.off_coef + static_cast<int>(reinterpret_cast<uintptr_t>(gco) & 3);
+    // dword w of row r (the row's first CW bytes from its dword phase on): batches of loads in flight
+    auto stage_rows = [&](int nrows, auto src_of) {
+        for (int base = 0; base < nrows * CWD; base += 256 * 4) {
+            uint32_t v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int idx = base + q * 256 + tid;
+                v[q] = 0;
+                if (idx >= nrows * CWD) continue;
+                const int r = fdiv(g.dcwd, idx), w = idx - r * CWD;
+                const uint8_t* gr = src_of(r);
+                if (!gr) continue;
+                const int ph = static_cast<int>(reinterpret_cast<uintptr_t>(gr) & 3);
+                const int lo = 4 * w - ph;  // the dword's first byte in the row
+                if (lo >= CW) continue;
+                if (lo >= 0 && lo + 4 <= CW) {
+                    v[q] = *reinterpret_cast<const uint32_t*>(gr + lo);
+                } else {
+                    for (int e = 0; e < 4; ++e)
+                        if (lo + e >= 0 && lo + e < CW) v[q] |= uint32_t(gr[lo + e]) << (8 * e);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int idx = base + q * 256 + tid;
+                if (idx >= nrows * CWD) continue;
+                const int r = fdiv(g.dcwd, idx), w = idx - r * CWD;
+                *reinterpret_cast<uint32_t*>(smem + g.off_rows + r * CWS + 4 * w) = v[q];
+            }
+        }
+    };
+    stage_rows(HR + u.cnt, row_src);
+    __syncthreads();
+    // window byte h of output row j (packet x = seq0 + j - T = row j + k - 1)
+    auto byte_at = [&](int j, int h) -> uint8_t {
+        const int s = fdiv(g.dk, h), i = h - s * k;
+        if ((fl[j] & 3) == kCopy) {
+            const int ro = rowoff[j + k - 1];
+            return ro < 0 ? 0 : smem[ro + s * n + i];
+        }
+        const uint8_t* coef = coefs + cord[j] * kn + i * n;
+        uint8_t acc = 0;
+        for (int q = 0; q < n; ++q) {  // symbol q of packet x - i + q
+            const uint8_t cf = coef[q];
+            const int r = j + k - 1 - i + q;
+            if (!cf || r > j + HR) continue;
+            const int ro = rowoff[r];
+            if (ro >= 0) acc ^= gmul(gexp, glog, cf, smem[ro + s * n + q]);
+        }
+        return acc;
+    };
+    if (tid < u.cnt) {  // header bytes first: they bound the copy
+        const int fate = fl[tid] & 3;
+        int ln = 0;
+        if (fate == kCopy || fate == kRecovered) {
+            const int hdr = byte_at(tid, 0) * 256 + byte_at(tid, 1);
+            ln = (fl[tid] & kRowClamp) ? min(hdr, L) : hdr;
+        }
+        lnS[tid] = ln;
+        cpS[tid] = min(ln, L);
+        a.out_len[u.row0 + tid] = ln;
+    }
+    __syncthreads();
+    uint8_t* gout = a.out + u.row0 * L;
+    const int ao = g.off_out + static_cast<int>(reinterpret_cast<uintptr_t>(gout) & 3);
+    for (int it = tid; it < u.cnt * LW; it += 256) {
+        const int j = fdiv(g.dlw, it), w = it - j * LW;
+        const int cp = cpS[j];
+        uint8_t* o = smem + ao + j * L + 4 * w;
+        if ((fl[j] & 3) == kCopy) {  // systematic bytes of the packet's own codeword
+            const int ro = rowoff[j + k - 1];
+            int s = fdiv(g.dk, 4 * w + 2), i = 4 * w + 2 - s * k;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int b = 4 * w + e;
+                if (b < L) o[e] = (b < cp && ro >= 0) ? smem[ro + s * n + i] : 0;
+                if (++i == k) i = 0, ++s;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int b = 4 * w + e;
+                if (b < L) o[e] = b < cp ? byte_at(j, b + 2) : 0;
+            }
+        }
+    }
+    __syncthreads();
+    burst_flush(gout, smem, ao, u.cnt * L, tid, 256);
+    if (u.lead != 0) return;
+    // the burst's last min(total, T + k) codewords into the ring (missing ones leave their slot as it is)
+    const int m = min(u.total, T + k), t0 = u.total - m;
+    int slot0 = HR + t0;  // LDS row of burst row t0
+    if (u.total > u.cnt) {  // they lie (partly) behind this chunk: staged again, rows 0 .. m-1
+        slot0 = 0;
+        for (int r = tid; r < m; r += 256) {
+            const uint8_t* gr = a.cw_in + (u.row0 + t0 + r) * CWR;
+            rowoff[r] = (a.flags[u.row0 + t0 + r] & kRowErased)
+                            ? -1 : g.off_rows + r * CWS + static_cast<int>(reinterpret_cast<uintptr_t>(gr) & 3);
+        }
+        __syncthreads();
+        auto tail_src = [&](int r) -> const uint8_t* {
+            return rowoff[r] < 0 ? nullptr : a.cw_in + (u.row0 + t0 + r) * CWR;
+        };
+        stage_rows(m, tail_src);
+        __syncthreads();
+    }
+    for (int tt = tid >> 6; tt < m; tt += 4) {
+        const int ro = rowoff[slot0 + tt];
+        if (ro >= 0) burst_flush(ringb + ((u.seq0 + t0 + tt) % kRR) * CWR, smem, ro, CW, tid & 63, 64);
+    }
+}
+
 }  // namespace
 }  // namespace fec
 
@@ -794,7 +1169,26 @@ struct fec_streams {
     size_t stage_cap[kStageBufs] = {};       // bytes of h_stage[b] (a burst call grows its buffer to its records)
     hipEvent_t done = nullptr;               // the last call's kernel (windows, rings, older d_stage free)
     bool poisoned = false;                   // a failed call left host and device state apart
+    // Mixed groups (fec_streams_create_mixed; empty otherwise, and then codec / g / W / SK / rules above
+    // are unused): the codes, each stream's code, the uniform row and slot strides, and the kernels'
+    // per-code tables.  A code's chunk sizes are fixed at create (for bursts of kBurstTP or more).
+    struct Code {
+        fec_codec* codec = nullptr;
+        fec::Geometry g;
+        std::shared_ptr<const fec::DecodeRules> rules;
+        int enc_tp = 0, enc_lds = 0, dec_tp = 0, dec_lds = 0;
+    };
+    std::vector<Code> codes;
+    std::vector<int32_t> code_of;
+    int cw_stride = 0;                       // the largest CW
+    size_t win_slot = 0;                     // the largest W * SK, rounded up to 16
+    fec::MixedEncCode* d_enc_codes = nullptr;
+    fec::MixedDecCode* d_dec_codes = nullptr;
     ~fec_streams() {
+        for (Code& c : codes)
+            if (c.codec) fec_codec_destroy(c.codec);
+        for (void* p : {static_cast<void*>(d_enc_codes), static_cast<void*>(d_dec_codes)})
+            if (p) (void)hipFree(p);
         for (hipEvent_t e : staged)
             if (e) (void)hipEventDestroy(e);
         if (done) (void)hipEventDestroy(done);
@@ -996,6 +1390,252 @@ void plan_burst_rows(fec::StreamPlanner& pl, int T, int kn, int64_t seq0, const 
     }
 }
 
+// What every group has besides its codes and planners (h->nstreams set): the step pool, the seq
+// counters, zeroed windows (wb bytes) and rings (rb bytes), the staging buffers and the events.
+int group_state_init(fec_streams* h, size_t wb, size_t rb, size_t stage_bytes) {
+    const int nstreams = h->nstreams;
+    {
+        const int hw = allowed_cpus();  // not hardware_concurrency: the process's cpuset may be smaller
+        int nth = std::max(1, std::min(hw > 1 ? hw - 1 : 1, 8));
+        if (const char* e = std::getenv("FEC_STREAMS_THREADS")) nth = std::max(1, std::atoi(e));
+        if (nth > 1 && nstreams >= 2 * kPoolMinItems) h->pool.reset(new StepPool(nth));
+    }
+    h->enc_seq.assign(nstreams, 0);
+    h->dec_seq.assign(nstreams, 0);
+    h->mark.assign(nstreams, 0);
+    FS_TRY(hipMalloc(&h->d_win, wb));
+    FS_TRY(hipMemset(h->d_win, 0, wb));
+    FS_TRY(hipMalloc(&h->d_ring, rb));
+    FS_TRY(hipMemset(h->d_ring, 0, rb));
+    h->stage_bytes = stage_bytes;
+    if (const char* e = std::getenv("FEC_STREAMS_UPLOAD")) h->upload = std::atoi(e) != 0;
+    for (int b = 0; b < fec_streams::kStageBufs; ++b) {
+        if (h->upload) FS_TRY(hipMalloc(&h->d_stage[b], h->stage_bytes));
+        FS_TRY(hipHostMalloc(&h->h_stage[b], h->stage_bytes, hipHostMallocMapped));
+        FS_TRY(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
+        h->stage_cap[b] = h->stage_bytes;
+        FS_TRY(hipEventCreateWithFlags(&h->staged[b], hipEventDisableTiming));
+        FS_TRY(hipEventRecord(h->staged[b], nullptr));
+    }
+    FS_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+    FS_TRY(hipEventRecord(h->done, nullptr));
+    return FEC_OK;
+}
+
+// ---- mixed groups ------------------------------------------------------------------------------
+
+constexpr int kMaxCodes = 64;
+
+// One code of a mixed group at payload size L: its geometry and its burst chunks, fixed for bursts of
+// kBurstTP or more, through the routines the one-code calls use.  FEC_ERR_ARG: a tuple that
+// fec_streams_create refuses (fec_codec_create's bounds, then the stream kernels'), or whose smallest
+// chunk does not fit the LDS.
+struct CodeFit {
+    fec::Geometry g;
+    int enc_tp = 0, enc_lds = 0, dec_tp = 0, dec_lds = 0;
+    fec::BurstEncArgs enc;
+    fec::BurstDecArgs dec;
+};
+int mixed_code_fit(int L, const int32_t* tbn, CodeFit* f) {
+    try {
+        f->g = fec::Geometry::make(L, tbn[0], tbn[1], tbn[2]);
+    } catch (const std::invalid_argument&) {
+        return FEC_ERR_ARG;
+    }
+    const fec::Geometry& g = f->g;
+    if (g.L > 1500 || g.B < g.N || g.n > fec::kMaxN - 1) return FEC_ERR_ARG;
+    if (g.T + g.k > fec::kRR || g.k > 16 || g.k * g.n > 16 * 32) return FEC_ERR_ARG;
+    f->enc = fec::BurstEncArgs{};
+    f->dec = fec::BurstDecArgs{};
+    f->enc_tp = burst_chunk(g, kBurstTP, g.n - 1, burst_enc_lds, &f->enc, &f->enc_lds);
+    f->dec_tp = burst_chunk(g, kBurstTP, g.T + g.k - 1, burst_dec_lds, &f->dec, &f->dec_lds);
+    return f->enc_tp && f->dec_tp ? FEC_OK : FEC_ERR_ARG;
+}
+
+// The chunks of one burst of `count` rows, cut every tp rows; returns the unit after them.
+fec::MixedUnit* mixed_fill_units(fec::MixedUnit* u, int id, int code, int count, int64_t row, int tp, int64_t seq) {
+    for (int lead = 0; lead < count; lead += tp, ++u) {
+        u->row0 = row + lead;
+        u->seq0 = seq + lead;
+        u->coef = 0;
+        u->id = id;
+        u->cnt = std::min(tp, count - lead);
+        u->lead = lead;
+        u->total = count;
+        u->code = code;
+        u->pad = 0;
+    }
+    return u;
+}
+
+// A mixed call's shape: counts (null: all 1) >= 1, ids distinct; R rows, nu chunks, and the largest
+// chunk LDS among the codes present in this call.
+int mixed_call_shape(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, bool enc, int64_t* R,
+                     int64_t* nu, int* lds) {
+    int maxc = 1;
+    *R = M;
+    if (counts)
+        if (int st = check_counts(counts, M, R, &maxc)) return st;
+    if (int st = check_ids(h, ids, M)) return st;
+    *nu = 0;
+    *lds = 0;
+    for (int m = 0; m < M; ++m) {
+        const fec_streams::Code& c = h->codes[h->code_of[ids[m]]];
+        const int tp = enc ? c.enc_tp : c.dec_tp;
+        *nu += ((counts ? counts[m] : 1) + tp - 1) / tp;
+        *lds = std::max(*lds, enc ? c.enc_lds : c.dec_lds);
+    }
+    return *nu > INT32_MAX ? FEC_ERR_ARG : FEC_OK;
+}
+
+// fec_streams_encode / fec_streams_encode_burst on a mixed group (counts null: one packet per stream).
+int mixed_encode(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, const uint8_t* d_payload,
+                 const int32_t* d_payload_len, uint8_t* d_codeword, int32_t* d_codeword_len, hipStream_t s) {
+    int64_t R = 0, nu = 0;
+    int lds = 0;
+    if (int st = mixed_call_shape(h, ids, counts, M, true, &R, &nu, &lds)) return st;
+    static int lds_raised = 0;
+    if (int st = burst_lds_allow(reinterpret_cast<const void*>(fec::fec_streams_encode_mixed_kernel), lds, &lds_raised))
+        return st;
+    int b = 0;
+    if (int st = stage_free(h, s, &b)) return st;
+    const size_t bytes = static_cast<size_t>(nu) * sizeof(fec::MixedUnit);
+    if (int st = stage_reserve(h, b, bytes)) {
+        h->poisoned = true;  // the buffer may be gone
+        return st;
+    }
+    fec::MixedUnit* u = static_cast<fec::MixedUnit*>(h->h_stage[b]);
+    int64_t row = 0;
+    for (int m = 0; m < M; ++m) {
+        const int id = ids[m], code = h->code_of[id], cnt = counts ? counts[m] : 1;
+        u = mixed_fill_units(u, id, code, cnt, row, h->codes[code].enc_tp, h->enc_seq[id]);
+        row += cnt;
+    }
+    if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
+    fec::MixedEncArgs a;
+    a.payload = d_payload;
+    a.len = d_payload_len;
+    a.units = static_cast<const fec::MixedUnit*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
+    a.codes = h->d_enc_codes;
+    a.win = h->d_win;
+    a.cw = d_codeword;
+    a.cw_len = d_codeword_len;
+    hipLaunchKernelGGL(fec::fec_streams_encode_mixed_kernel, dim3(static_cast<unsigned>(nu)), dim3(256), lds, s, a);
+    FS_TRY(hipGetLastError());
+    FS_TRY(hipEventRecord(h->done, s));
+    FS_TRY(hipEventRecord(h->staged[b], s));
+    h->buf = (b + 1) % fec_streams::kStageBufs;
+    for (int m = 0; m < M; ++m) h->enc_seq[ids[m]] += counts ? counts[m] : 1;
+    return FEC_OK;
+}
+
+// fec_streams_decode / fec_streams_decode_burst on a mixed group (counts null: one packet per stream):
+// fec_streams_decode_burst's host side with each stream's own planner, T, k x n and chunk size.
+int mixed_decode(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, const uint8_t* erasure,
+                 const uint8_t* d_codeword, uint8_t* d_payload_out, int32_t* d_payload_len, hipStream_t s) {
+    int64_t R = 0, nu = 0;
+    int lds = 0;
+    if (int st = mixed_call_shape(h, ids, counts, M, false, &R, &nu, &lds)) return st;
+    static int lds_raised = 0;
+    if (int st = burst_lds_allow(reinterpret_cast<const void*>(fec::fec_streams_decode_mixed_kernel), lds, &lds_raised))
+        return st;
+    int b = 0;
+    if (int st = stage_free(h, s, &b)) return st;
+    // The symbolic decoders advance before the launch: a failure from here on leaves the host planners
+    // ahead of the device rings, and the group refuses every later call.
+    struct Poison {
+        fec_streams* h;
+        bool armed = true;
+        ~Poison() { if (armed) h->poisoned = true; }
+    } poison{h};
+    try {
+        // streams are independent: contiguous parts of them, one per thread; a part's recovered rows
+        // keep their coefficient blocks in row order
+        const int np = (h->pool && R >= 2 * kPoolMinItems) ? h->pool->parts() : 1;
+        std::vector<int64_t> row_at(M + 1, 0), unit_at(M + 1, 0);
+        for (int m = 0; m < M; ++m) {
+            const int cnt = counts ? counts[m] : 1, tp = h->codes[h->code_of[ids[m]]].dec_tp;
+            row_at[m + 1] = row_at[m] + cnt;
+            unit_at[m + 1] = unit_at[m] + (cnt + tp - 1) / tp;
+        }
+        std::vector<uint8_t> flags(static_cast<size_t>(R));
+        std::vector<fec::MixedUnit> units(static_cast<size_t>(nu));
+        std::vector<std::vector<uint8_t>> coefs(np);
+        std::atomic<bool> failed{false};
+        auto part = [&](int p) {
+            if (p < 0 || p >= np) return;
+            try {
+                const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
+                const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
+                int64_t cbytes = 0;  // coefficient bytes of this part's chunks so far
+                for (int m = m0; m < m1; ++m) {
+                    const int id = ids[m], code = h->code_of[id], cnt = counts ? counts[m] : 1;
+                    const fec_streams::Code& c = h->codes[code];
+                    const int kn = c.g.k * c.g.n;
+                    mixed_fill_units(units.data() + unit_at[m], id, code, cnt, row_at[m], c.dec_tp, h->dec_seq[id]);
+                    plan_burst_rows(*h->planners[id], c.g.T, kn, h->dec_seq[id], erasure + row_at[m], cnt,
+                                    flags.data() + row_at[m], coefs[p]);
+                    h->dec_seq[id] += cnt;
+                    for (int64_t ui = unit_at[m]; ui < unit_at[m + 1]; ++ui) {
+                        fec::MixedUnit& u = units[ui];
+                        u.coef = cbytes;
+                        for (int j = 0; j < u.cnt; ++j)
+                            if ((flags[u.row0 + j] & 3) == fec::kRecovered) cbytes += kn;
+                    }
+                }
+            } catch (...) {
+                failed.store(true);
+            }
+        };
+        if (np > 1)
+            h->pool->run(part);
+        else
+            part(0);
+        if (failed.load()) return FEC_ERR_ARG;
+        // staging: units | row flags | coefficient blocks
+        const size_t off_flags = align16(static_cast<size_t>(nu) * sizeof(fec::MixedUnit));
+        const size_t off_coef = align16(off_flags + static_cast<size_t>(R));
+        size_t ncoef = 0;
+        for (const auto& c : coefs) ncoef += c.size();
+        const size_t bytes = off_coef + ncoef + 16;
+        if (int st = stage_reserve(h, b, bytes)) return st;
+        uint8_t* hs = static_cast<uint8_t*>(h->h_stage[b]);
+        size_t cbase = 0;
+        for (int p = 0; p < np; ++p) {  // a part's blocks follow those of the parts before it
+            const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
+            const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
+            if (cbase)
+                for (int64_t ui = unit_at[m0]; ui < unit_at[m1]; ++ui) units[ui].coef += static_cast<int64_t>(cbase);
+            if (!coefs[p].empty()) std::memcpy(hs + off_coef + cbase, coefs[p].data(), coefs[p].size());
+            cbase += coefs[p].size();
+        }
+        std::memcpy(hs, units.data(), units.size() * sizeof(fec::MixedUnit));
+        std::memcpy(hs + off_flags, flags.data(), flags.size());
+        if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
+        const uint8_t* rec = static_cast<const uint8_t*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
+        fec::MixedDecArgs a;
+        a.cw_in = d_codeword;
+        a.units = reinterpret_cast<const fec::MixedUnit*>(rec);
+        a.codes = h->d_dec_codes;
+        a.flags = rec + off_flags;
+        a.coefs = rec + off_coef;
+        a.ring = h->d_ring;
+        a.out = d_payload_out;
+        a.out_len = d_payload_len;
+        hipLaunchKernelGGL(fec::fec_streams_decode_mixed_kernel, dim3(static_cast<unsigned>(nu)), dim3(256), lds, s, a);
+        FS_TRY(hipGetLastError());
+        FS_TRY(hipEventRecord(h->done, s));
+        FS_TRY(hipEventRecord(h->staged[b], s));
+        h->buf = (b + 1) % fec_streams::kStageBufs;
+        poison.armed = false;
+        return FEC_OK;
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    } catch (...) {
+        return FEC_ERR_ARG;
+    }
+}
+
 }  // namespace
 
 int fec::stream_encode_one(const CodecView& v, uint8_t* win, const uint8_t* payload, int payload_len, int64_t seq,
@@ -1072,33 +1712,10 @@ int fec_streams_create(int max_payload, int T, int B, int N, int nstreams, fec_s
         h->rules = fec::shared_decode_rules(T, B, N);
         h->planners.resize(nstreams);
         for (auto& p : h->planners) p.reset(new fec::StreamPlanner(g, h->rules.get()));
-        {
-            const int hw = allowed_cpus();  // not hardware_concurrency: the process's cpuset may be smaller
-            int nth = std::max(1, std::min(hw > 1 ? hw - 1 : 1, 8));
-            if (const char* e = std::getenv("FEC_STREAMS_THREADS")) nth = std::max(1, std::atoi(e));
-            if (nth > 1 && nstreams >= 2 * kPoolMinItems) h->pool.reset(new StepPool(nth));
-        }
-        h->enc_seq.assign(nstreams, 0);
-        h->dec_seq.assign(nstreams, 0);
-        h->mark.assign(nstreams, 0);
         const size_t wb = static_cast<size_t>(nstreams) * h->W * h->SK;
         const size_t rb = static_cast<size_t>(nstreams) * fec::kRR * g.CW;
-        FS_TRY(hipMalloc(&h->d_win, wb));
-        FS_TRY(hipMemset(h->d_win, 0, wb));
-        FS_TRY(hipMalloc(&h->d_ring, rb));
-        FS_TRY(hipMemset(h->d_ring, 0, rb));
-        h->stage_bytes = static_cast<size_t>(nstreams) * (sizeof(fec::StreamItem) + g.k * g.n + 16) + 64;
-        if (const char* e = std::getenv("FEC_STREAMS_UPLOAD")) h->upload = std::atoi(e) != 0;
-        for (int b = 0; b < fec_streams::kStageBufs; ++b) {
-            if (h->upload) FS_TRY(hipMalloc(&h->d_stage[b], h->stage_bytes));
-            FS_TRY(hipHostMalloc(&h->h_stage[b], h->stage_bytes, hipHostMallocMapped));
-            FS_TRY(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
-            h->stage_cap[b] = h->stage_bytes;
-            FS_TRY(hipEventCreateWithFlags(&h->staged[b], hipEventDisableTiming));
-            FS_TRY(hipEventRecord(h->staged[b], nullptr));
-        }
-        FS_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-        FS_TRY(hipEventRecord(h->done, nullptr));
+        const size_t stage = static_cast<size_t>(nstreams) * (sizeof(fec::StreamItem) + g.k * g.n + 16) + 64;
+        if (int st = group_state_init(h.get(), wb, rb, stage)) return st;
         *out = h.release();
         return FEC_OK;
     } catch (const std::bad_alloc&) {
@@ -1119,6 +1736,9 @@ int fec_streams_encode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
     if (!h || M < 0 || M > h->nstreams || (M > 0 && (!ids || !d_payload || !d_codeword || !d_codeword_len)))
         return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
+    if (!h->codes.empty())
+        return mixed_encode(h, ids, nullptr, M, d_payload, d_payload_len, d_codeword, d_codeword_len,
+                            static_cast<hipStream_t>(stream));
     if (int st = check_ids(h, ids, M)) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int b = 0;
@@ -1172,6 +1792,9 @@ int fec_streams_decode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
                                                      !d_payload_len)))
         return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
+    if (!h->codes.empty())
+        return mixed_decode(h, ids, nullptr, M, erasure, d_codeword, d_payload_out, d_payload_len,
+                            static_cast<hipStream_t>(stream));
     static const bool dbg = std::getenv("FEC_STREAMS_DEBUG") != nullptr;  // per-phase host times
     const auto t0 = std::chrono::steady_clock::now();
     if (int st = check_ids(h, ids, M)) return st;
@@ -1274,6 +1897,9 @@ int fec_streams_encode_burst(fec_streams* h, const int32_t* ids, const int32_t* 
         (M > 0 && (!ids || !counts || !d_payload || !d_codeword || !d_codeword_len)))
         return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
+    if (!h->codes.empty())
+        return mixed_encode(h, ids, counts, M, d_payload, d_payload_len, d_codeword, d_codeword_len,
+                            static_cast<hipStream_t>(stream));
     int64_t R = 0;
     int maxc = 0;
     if (int st = check_counts(counts, M, &R, &maxc)) return st;
@@ -1324,6 +1950,9 @@ int fec_streams_decode_burst(fec_streams* h, const int32_t* ids, const int32_t* 
         (M > 0 && (!ids || !counts || !erasure || !d_codeword || !d_payload_out || !d_payload_len)))
         return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
+    if (!h->codes.empty())
+        return mixed_decode(h, ids, counts, M, erasure, d_codeword, d_payload_out, d_payload_len,
+                            static_cast<hipStream_t>(stream));
     int64_t R = 0;
     int maxc = 0;
     if (int st = check_counts(counts, M, &R, &maxc)) return st;
@@ -1470,6 +2099,135 @@ int fec_streams_state(const fec_streams* h, int id, int64_t* sent, int64_t* rece
     if (sent) *sent = h->enc_seq[id];
     if (received) *received = h->dec_seq[id];
     return FEC_OK;
+}
+
+int fec_streams_mixed_fit(int max_payload, const int32_t* tuples, int ncodes, int32_t* enc_chunk, int32_t* enc_lds,
+                          int32_t* dec_chunk, int32_t* dec_lds) {
+    if (!tuples || ncodes < 1 || ncodes > kMaxCodes || !enc_chunk || !enc_lds || !dec_chunk || !dec_lds)
+        return FEC_ERR_ARG;
+    for (int c = 0; c < ncodes; ++c) {
+        CodeFit f;
+        if (int st = mixed_code_fit(max_payload, tuples + 3 * c, &f)) return st;
+        enc_chunk[c] = f.enc_tp, enc_lds[c] = f.enc_lds, dec_chunk[c] = f.dec_tp, dec_lds[c] = f.dec_lds;
+    }
+    return FEC_OK;
+}
+
+int fec_streams_create_mixed(int max_payload, const int32_t* tuples, int ncodes, const int32_t* code_of, int nstreams,
+                             fec_streams** out) {
+    if (!out) return FEC_ERR_ARG;
+    *out = nullptr;
+    if (!tuples || !code_of || ncodes < 1 || ncodes > kMaxCodes || nstreams <= 0) return FEC_ERR_ARG;
+    for (int i = 0; i < nstreams; ++i)
+        if (code_of[i] < 0 || code_of[i] >= ncodes) return FEC_ERR_ARG;
+    try {
+        std::vector<CodeFit> fit(ncodes);
+        for (int c = 0; c < ncodes; ++c)
+            if (int st = mixed_code_fit(max_payload, tuples + 3 * c, &fit[c])) return st;
+        std::unique_ptr<fec_streams> h(new fec_streams());
+        h->nstreams = nstreams;
+        h->codes.resize(ncodes);
+        for (int c = 0; c < ncodes; ++c) {
+            fec_streams::Code& code = h->codes[c];
+            const int32_t* t = tuples + 3 * c;
+            if (int st = fec_codec_create(max_payload, t[0], t[1], t[2], &code.codec)) return st;
+            code.g = fit[c].g;
+            code.rules = fec::shared_decode_rules(t[0], t[1], t[2]);
+            code.enc_tp = fit[c].enc_tp, code.enc_lds = fit[c].enc_lds;
+            code.dec_tp = fit[c].dec_tp, code.dec_lds = fit[c].dec_lds;
+            h->cw_stride = std::max(h->cw_stride, code.g.CW);
+            h->win_slot = std::max(h->win_slot, align16(static_cast<size_t>(fit[c].enc.W) * fit[c].enc.SK));
+        }
+        h->code_of.assign(code_of, code_of + nstreams);
+        h->planners.resize(nstreams);
+        for (int i = 0; i < nstreams; ++i) {
+            const fec_streams::Code& code = h->codes[code_of[i]];
+            h->planners[i].reset(new fec::StreamPlanner(code.g, code.rules.get()));
+        }
+        // the kernels' tables: a code's geometry at its chunk sizes, its constants, the group's strides
+        std::vector<fec::MixedEncCode> et(ncodes);
+        std::vector<fec::MixedDecCode> dt(ncodes);
+        size_t kn_max = 0;
+        for (int c = 0; c < ncodes; ++c) {
+            fec::CodecView v;
+            if (int st = fec::codec_view(h->codes[c].codec, &v)) return st;
+            et[c].g = fit[c].enc;
+            et[c].g.ptab = v.ptab;
+            et[c].slot = static_cast<int64_t>(h->win_slot);
+            et[c].cwr = h->cw_stride;
+            et[c].pad = 0;
+            dt[c].g = fit[c].dec;
+            dt[c].g.gf = v.gf;
+            dt[c].cwr = h->cw_stride;
+            dt[c].pad = 0;
+            kn_max = std::max(kn_max, static_cast<size_t>(v.k) * v.n);
+        }
+        FS_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_enc_codes), et.size() * sizeof(et[0])));
+        FS_TRY(hipMemcpy(h->d_enc_codes, et.data(), et.size() * sizeof(et[0]), hipMemcpyHostToDevice));
+        FS_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_dec_codes), dt.size() * sizeof(dt[0])));
+        FS_TRY(hipMemcpy(h->d_dec_codes, dt.data(), dt.size() * sizeof(dt[0]), hipMemcpyHostToDevice));
+        const size_t wb = static_cast<size_t>(nstreams) * h->win_slot;
+        const size_t rb = static_cast<size_t>(nstreams) * fec::kRR * h->cw_stride;
+        const size_t stage = static_cast<size_t>(nstreams) * (sizeof(fec::MixedUnit) + 1 + kn_max + 16) + 64;
+        if (int st = group_state_init(h.get(), wb, rb, stage)) return st;
+        *out = h.release();
+        return FEC_OK;
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    } catch (...) {
+        return FEC_ERR_ARG;
+    }
+}
+
+int fec_streams_codes(const fec_streams* h, int* ncodes, int* cw_stride) {
+    if (!h) return FEC_ERR_ARG;
+    if (ncodes) *ncodes = h->codes.empty() ? 1 : static_cast<int>(h->codes.size());
+    if (cw_stride) *cw_stride = h->codes.empty() ? h->g.CW : h->cw_stride;
+    return FEC_OK;
+}
+
+int fec_streams_stream_geometry(const fec_streams* h, int id, int* code, int* T, int* k, int* n, int* S, int* CW) {
+    if (!h || id < 0 || id >= h->nstreams) return FEC_ERR_ARG;
+    const int c = h->codes.empty() ? 0 : h->code_of[id];
+    const fec::Geometry& g = h->codes.empty() ? h->g : h->codes[c].g;
+    if (code) *code = c;
+    if (T) *T = g.T;
+    if (k) *k = g.k;
+    if (n) *n = g.n;
+    if (S) *S = g.S;
+    if (CW) *CW = g.CW;
+    return FEC_OK;
+}
+
+int fec_streams_set_code(fec_streams* h, int id, int code) {
+    if (!h || id < 0 || id >= h->nstreams || code < 0 || code >= (h->codes.empty() ? 1 : static_cast<int>(h->codes.size())))
+        return FEC_ERR_ARG;
+    try {
+        // host work only: the kernels read a window or ring row only for a packet seq >= 0 of the
+        // stream's current life, so the slot's old bytes are never seen (see the mixed kernels)
+        std::unique_ptr<fec::StreamPlanner> pl(
+            h->codes.empty() ? new fec::StreamPlanner(h->g, h->rules.get())
+                             : new fec::StreamPlanner(h->codes[code].g, h->codes[code].rules.get()));
+        if (h->codes.empty()) {
+            // a one-code group's one-packet decode kernel reads the ring rows of packets before the
+            // stream's start as the zero rows they were at create: zero them again, between the
+            // last call and the next (both are ordered by `done`)
+            if (h->poisoned) return FEC_ERR_HIP;
+            uint8_t* ring = h->d_ring + static_cast<size_t>(id) * fec::kRR * h->g.CW;
+            FS_TRY(hipStreamWaitEvent(nullptr, h->done, 0));
+            FS_TRY(hipMemsetAsync(ring, 0, static_cast<size_t>(fec::kRR) * h->g.CW, nullptr));
+            FS_TRY(hipEventRecord(h->done, nullptr));
+        }
+        h->planners[id] = std::move(pl);
+        if (!h->codes.empty()) h->code_of[id] = code;
+        h->enc_seq[id] = 0;
+        h->dec_seq[id] = 0;
+        return FEC_OK;
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    } catch (...) {
+        return FEC_ERR_ARG;
+    }
 }
 
 }  // extern "C"

@@ -218,6 +218,46 @@ int fec_streams_plan_burst_host(int max_payload, int T, int B, int N, const uint
                                 const int32_t *counts, int ncounts, uint8_t *fate);
 /* Packets stream `id` has sent (encoded) and received (decoded) so far. */
 int fec_streams_state(const fec_streams *group, int id, int64_t *sent, int64_t *received);
+/* Mixed groups: every stream has its own code, and one call codes streams of different (T,B,N) in
+ * one launch per direction -- the node that serves many flows of the adaptive loop, each on the code
+ * its own loss calls for.  tuples: ncodes x {T,B,N} (1 <= ncodes <= 64, equal tuples may repeat),
+ * code_of: nstreams indices into it.  FEC_ERR_ARG, nothing created: a tuple fec_streams_create
+ * refuses at this max_payload, a tuple whose smallest burst chunk does not fit the LDS in either
+ * direction (fec_streams_mixed_fit), a code index outside [0, ncodes), a null pointer.
+ * The result is an ordinary group: fec_streams_encode / _decode / _encode_burst / _decode_burst /
+ * _state / _destroy take it unchanged, with this row layout: payload rows are max_payload bytes;
+ * codeword rows, in and out, have one stride for the whole group, cw_stride = the largest CW of its
+ * codes (a one-code group is this case with cw_stride = CW).  A stream's codeword is the first CW
+ * bytes of its row, CW its own code's; encode writes zero into the rest of the row, decode never
+ * reads it.  Output row m of a decode call is packet seq - T of stream ids[m], with its own T.  Per
+ * stream, all its rows over all calls equal fec_encode_batch / fec_decode_batch of its own (T,B,N)
+ * over its whole sequence, whatever the cutting into one-packet calls and bursts and whichever
+ * streams shared its calls.  Both directions run the two mixed kernels (fec_streams.hip: the burst
+ * kernels' chunks, each with its code's geometry from a table in device memory), one-packet calls
+ * as chunks of one packet; a code's chunk size is fixed at create, and a launch takes the LDS of the
+ * largest chunk among the codes present in that call.  Device state per stream: a window slot of
+ * max_c((n_c-1) S_c k_c) bytes and a ring of 64 rows of cw_stride bytes. */
+int fec_streams_create_mixed(int max_payload, const int32_t *tuples, int ncodes,
+                             const int32_t *code_of, int nstreams, fec_streams **out);
+/* The number of codes of a group (1 for fec_streams_create's) and its codeword row stride. */
+int fec_streams_codes(const fec_streams *group, int *ncodes, int *cw_stride);
+/* Stream `id`'s code index and that code's geometry (any pointer may be NULL). */
+int fec_streams_stream_geometry(const fec_streams *group, int id, int *code, int *T, int *k, int *n,
+                                int *S, int *CW);
+/* Makes stream `id` a fresh encoder and a fresh decoder of code `code`, as an adaptive endpoint
+ * does when it constructs a new FEC_Encoder at a switch: both seq counters go to 0 and the
+ * decoder's symbolic state is new.  Host work on a mixed group (calls already queued carry their
+ * own seqs; the kernels never read a stream's device state from before seq 0).  The old code's
+ * last T packets are never output: a caller that wants them keeps the old stream id alive beside
+ * the new one through the double-coded seqs.  On a group made by fec_streams_create only code 0
+ * is accepted, and resets the stream.  FEC_ERR_ARG (group unchanged): id or code out of range. */
+int fec_streams_set_code(fec_streams *group, int id, int code);
+/* Host only, no device call: per code the packets per chunk and the LDS bytes of the mixed group's
+ * encode and decode chunks (ncodes entries each), through the routines the calls use; a chunk lies
+ * between the packets it needs in front of it (n-1 / T+k-1) and 32.  FEC_ERR_ARG if any tuple is
+ * refused or does not fit, ncodes is outside [1, 64] or a pointer is null. */
+int fec_streams_mixed_fit(int max_payload, const int32_t *tuples, int ncodes, int32_t *enc_chunk,
+                          int32_t *enc_lds, int32_t *dec_chunk, int32_t *dec_lds);
 
 /* ---- per-kernel timing (HIP events recorded on the launch stream) --------------------------- */
 #define FEC_KERNEL_ENCODE 0
