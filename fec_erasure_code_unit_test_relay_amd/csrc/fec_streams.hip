@@ -16,8 +16,8 @@
 // A burst call (fec_streams_encode_burst / fec_streams_decode_burst) hands over several consecutive
 // packets of each stream and equals that many one-packet calls; its kernels work on chunks of a
 // burst and touch the per-stream state only at the burst's two ends (see "bursts" below).
-// A mixed group (fec_streams_create_mixed) gives every stream its own (T,B,N): its calls run the burst
-// kernels' chunks with each chunk's geometry taken from a per-code table (see "mixed groups" below).
+// A mixed group (fec_streams_create_mixed) gives every stream its own (T,B,N): its calls run the same
+// chunk bodies through kernels that take each chunk's geometry from a per-code table (see "bursts").
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -246,9 +246,29 @@ __global__ __launch_bounds__(256) void fec_streams_encode_kernel(StreamsEncArgs 
     }
 }
 
+// Packet it.x from the symbols sym(packet, offset): a copy or the planner's recovery coefficients.
 template <class Sym>
 __device__ __forceinline__ void stream_output(const StreamsDecArgs& a, const StreamItem& it, uint8_t* orow, int m,
-                                              int lane, const uint8_t* gexp, const uint8_t* glog, Sym sym);
+                                              int lane, const uint8_t* gexp, const uint8_t* glog, Sym sym) {
+    const int L = a.L, k = a.k, n = a.n;
+    const uint8_t* coef = a.coefs + static_cast<int64_t>(it.coef) * k * n;
+    // header bytes 0, 1 (sub-stream 0, positions 0 and 1 -> (1/k)*n + 1%k) first: they bound the copy
+    auto byte_at = [&](int h) -> uint8_t {
+        const int s = h / k, i = h - s * k;
+        if (it.fate == kCopy) return sym(it.x, s * n + i);
+        uint8_t acc = 0;
+        for (int q = 0; q < n; ++q) {
+            const uint8_t c = coef[i * n + q];
+            if (c) acc ^= gmul(gexp, glog, c, sym(it.x - i + q, s * n + q));
+        }
+        return acc;
+    };
+    const int hdr = byte_at(0) * 256 + byte_at(1);
+    const int ln = it.clamp ? min(hdr, L) : hdr;
+    const int cp = min(ln, L);
+    for (int b = lane; b < L; b += 64) orow[b] = b < cp ? byte_at(b + 2) : 0;
+    if (lane == 0) a.out_len[m] = ln;
+}
 
 // One wave per packet: store the received codeword in the stream's ring, output packet x.
 __global__ __launch_bounds__(256) void fec_streams_decode_kernel(StreamsDecArgs a) {
@@ -296,29 +316,6 @@ __global__ __launch_bounds__(256) void fec_streams_decode_kernel(StreamsDecArgs 
     }
 }
 
-template <class Sym>
-__device__ __forceinline__ void stream_output(const StreamsDecArgs& a, const StreamItem& it, uint8_t* orow, int m,
-                                              int lane, const uint8_t* gexp, const uint8_t* glog, Sym sym) {
-    const int L = a.L, k = a.k, n = a.n;
-    const uint8_t* coef = a.coefs + static_cast<int64_t>(it.coef) * k * n;
-    // header bytes 0, 1 (sub-stream 0, positions 0 and 1 -> (1/k)*n + 1%k) first: they bound the copy
-    auto byte_at = [&](int h) -> uint8_t {
-        const int s = h / k, i = h - s * k;
-        if (it.fate == kCopy) return sym(it.x, s * n + i);
-        uint8_t acc = 0;
-        for (int q = 0; q < n; ++q) {
-            const uint8_t c = coef[i * n + q];
-            if (c) acc ^= gmul(gexp, glog, c, sym(it.x - i + q, s * n + q));
-        }
-        return acc;
-    };
-    const int hdr = byte_at(0) * 256 + byte_at(1);
-    const int ln = it.clamp ? min(hdr, L) : hdr;
-    const int cp = min(ln, L);
-    for (int b = lane; b < L; b += 64) orow[b] = b < cp ? byte_at(b + 2) : 0;
-    if (lane == 0) a.out_len[m] = ln;
-}
-
 // ---- bursts: counts[m] consecutive packets of each stream per call ---------------------------
 // A burst is cut into chunks of at most TP packets, one workgroup each.  A chunk takes the packets
 // in front of it that it needs (the encoder's n-1 windows, the decoder's T+k-1 codewords) from the
@@ -326,6 +323,21 @@ __device__ __forceinline__ void stream_output(const StreamsDecArgs& a, const Str
 // reads them from the stream's ring.  The same workgroup, after a barrier, writes the ring with the
 // burst's last packets (from the call's rows): no other workgroup of the launch touches that
 // stream's ring, which takes TP >= n-1 (T+k-1) whenever a burst has more than one chunk.
+//
+// Each direction has one chunk body (burst_encode_chunk, burst_decode_chunk) and two kernels that
+// differ only in where the chunk's geometry comes from: a one-code group's kernel has it in its
+// arguments, sized to the call's largest burst; a mixed group's kernel takes it from a per-code table
+// in device memory, sized at create.  A chunk's unit names its code, and since the code is the same
+// for the whole workgroup (read through readfirstlane) the table entry arrives by scalar loads, once,
+// before the kernel's first store.
+// A group's rows and slots have one stride for all its codes: codeword rows of the largest CW (a
+// stream's codeword is the first CW bytes of its row, its own code's CW; encode zeroes the rest,
+// decode never reads it), a window slot of `slot` bytes and a ring slot of kRR rows per stream, in
+// which a stream uses its own W, SK and CW.  In a one-code group the stride is CW.
+// A stream that changes code (fec_streams_set_code) starts again at seq 0 in the same slots with
+// nothing cleared: a body reads a window / ring row only for a packet seq >= 0 of the stream's
+// current life (the `u.seq0 + p >= 0` tests), and every such window row was written in this life; a
+// ring row of a missing packet keeps older bytes, which meet only zero coefficients.
 
 struct FastDiv {  // x / d by one multiply, exact while x * d < 2^32
     uint32_t m, d;
@@ -340,394 +352,78 @@ __device__ __forceinline__ int fdiv(FastDiv f, int x) {
 struct BurstUnit {   // one chunk = one workgroup
     int64_t row0;    // its first row in the call's row arrays
     int64_t seq0;    // that row's sequence number in its stream
+    int64_t coef;    // decode: byte offset of the chunk's first coefficient block (its recovered rows, in row order)
     int32_t id;
-    int32_t cnt;     // rows of the chunk (<= TP)
+    int32_t cnt;     // rows of the chunk (<= the code's TP)
     int32_t lead;    // rows of the burst in front of the chunk (0: the first chunk)
     int32_t total;   // rows of the burst
-    int32_t coef0;   // decode: index of the chunk's first coefficient block (its recovered rows, in row order)
+    int32_t code;    // index in the mixed kernels' table (0 in a one-code group)
     int32_t pad;
 };
 constexpr uint8_t kRowClamp = 4, kRowErased = 8;  // decode row flags: fate | clamp | erased
 
-struct BurstEncArgs {
-    const uint8_t* payload;  // R rows of L bytes
-    const int32_t* len;      // R payload sizes (null: all L)
-    const BurstUnit* units;
-    uint8_t* win;            // [streams][W][SK] window ring
-    uint8_t* cw;             // R rows of CW bytes
-    int32_t* cw_len;
-    const uint32_t* ptab;    // [k][n-k][8] gf_mul4x tables
+struct BurstEncGeom {      // a chunk's geometry (burst_enc_lds) and its code's constants
+    const uint32_t* ptab;  // [k][n-k][8] gf_mul4x tables
     int L, k, n, S, SP, NS4, CW, SK, SKS, W, TP, ROWS;
     int off_planes, off_io, off_ring, off_len;  // dynamic LDS carve-up (bytes, multiples of 16)
     FastDiv dk, dns4, dnq;
 };
-
-struct BurstDecArgs {
-    const uint8_t* cw_in;    // R rows of CW bytes (rows of erased packets are not read)
-    const BurstUnit* units;
-    const uint8_t* flags;    // R bytes: fate | kRowClamp | kRowErased
-    const uint8_t* coefs;    // the recovered rows' k x n blocks
-    uint8_t* ring;           // [streams][kRR][CW]
+struct BurstDecGeom {  // burst_dec_lds
     const uint8_t* gf;
-    uint8_t* out;            // R rows of L bytes
-    int32_t* out_len;
     int L, k, n, CW, CWS, CWD, LW, T, TP, HR, ROWS;
     int off_rows, off_out, off_coef, off_meta;  // dynamic LDS carve-up
     FastDiv dk, dlw, dcwd;
 };
 
-// One workgroup per chunk.  LDS: the parity tables; the windows of the chunk's packets and of the
-// n-1 in front of them as position planes [i][row][sub-stream] (the four sub-streams of one
-// gf_mul4x sit in one dword); the chunk's payload rows, later its codewords; the ring's rows.
-__global__ __launch_bounds__(256) void fec_streams_encode_burst_kernel(BurstEncArgs a) {
-    extern __shared__ __align__(16) uint8_t smem[];
-    const int tid = threadIdx.x;
-    const BurstUnit u = a.units[blockIdx.x];
-    const int L = a.L, k = a.k, n = a.n, S = a.S, SP = a.SP, NS4 = a.NS4, CW = a.CW, SK = a.SK, SKS = a.SKS;
-    const int W = a.W, ROWS = a.ROWS, np = n - k, H = n - 1;
-    uint32_t* tab = reinterpret_cast<uint32_t*>(smem);
-    uint8_t* planes = smem + a.off_planes;
-    int* lens = reinterpret_cast<int*>(smem + a.off_len);  // per row: payload size; -1 no packet; -2 ring row
-    for (int i = tid; i < k * np * 8; i += 256) tab[i] = a.ptab[i];
-    const int hb = min(H, u.lead);  // rows in front of the chunk that lie in the burst
-    const uint8_t* ringb = a.win + static_cast<int64_t>(u.id) * W * SK;
-    // row r = packet seq0 + r - H
-    for (int r = tid; r < ROWS; r += 256) {
-        const int p = r - H;
-        int v = -1;
-        if (p < u.cnt) {
-            if (p >= -hb)
-                v = a.len ? min(max(a.len[u.row0 + p], 0), L) : L;
-            else if (u.seq0 + p >= 0)
-                v = -2;
-        }
-        lens[r] = v;
-    }
-    const uint8_t* g0 = a.payload + (u.row0 - hb) * L;
-    burst_stage(smem, a.off_io, g0, (hb + u.cnt) * L, tid, 256);
-    for (int r = 0; r < H - hb; ++r) {  // ring rows (first chunk only)
-        const int64_t seq = u.seq0 + r - H;
-        if (seq >= 0) burst_stage(smem, a.off_ring + r * SKS, ringb + (seq % W) * SK, SK, tid, 256);
-    }
-    __syncthreads();
-    // payload byte b of row r at smem[rawoff + r * L + b]
-    const int rawoff = a.off_io + static_cast<int>(reinterpret_cast<uintptr_t>(g0) & 3) - (H - hb) * L;
-    const int nq = (SK + 3) >> 2;
-    const FastDiv dnq = a.dnq;
-    // the dword at any LDS byte offset: two aligned reads
-    auto lds_word = [&](int off) -> uint32_t {
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(smem + (off & ~3));
-        return __builtin_amdgcn_alignbyte(w[1], w[0], off & 3);
-    };
-    for (int idx = tid; idx < ROWS * nq; idx += 256) {  // window bytes 4q .. 4q+3 of row r
-        const int r = fdiv(dnq, idx), q = idx - r * nq;
-        const int ln = lens[r];
-        uint32_t w = 0;  // [len_hi, len_lo, payload, zero pad] (Encoder.cpp:75-83)
-        if (ln >= 0) {
-            w = lds_word(rawoff + r * L + 4 * q - 2) & keep_bytes(ln + 2 - 4 * q);
-            if (q == 0) w = (w & 0xffff0000u) | static_cast<uint32_t>(ln >> 8) | (static_cast<uint32_t>(ln & 0xff) << 8);
-        } else if (ln == -2) {
-            const uint8_t* g = ringb + ((u.seq0 + r - H) % W) * SK;
-            w = lds_word(a.off_ring + r * SKS + static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3) + 4 * q);
-        }
-        int s = fdiv(a.dk, 4 * q), i = 4 * q - s * k;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (4 * q + e < SK) planes[(i * ROWS + r) * SP + s] = static_cast<uint8_t>(w >> (8 * e));
-            if (++i == k) i = 0, ++s;
-        }
-    }
-    __syncthreads();  // the planes are complete; the payload rows give way to the codewords
-    uint8_t* gcw = a.cw + u.row0 * CW;
-    const int ao = a.off_io + static_cast<int>(reinterpret_cast<uintptr_t>(gcw) & 3);
-    uint8_t* out = smem + ao;
-    for (int idx = tid; idx < u.cnt * nq; idx += 256) {  // systematic bytes
-        const int p = fdiv(dnq, idx), q = idx - p * nq;
-        int s = fdiv(a.dk, 4 * q), i = 4 * q - s * k;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (4 * q + e < SK) out[p * CW + s * n + i] = planes[(i * ROWS + p + H) * SP + s];
-            if (++i == k) i = 0, ++s;
-        }
-    }
-    // parity column j of four sub-streams: XOR_i G[i][j] * X_{t-(j-i)}[s][i]; rows without a packet are zero
-    for (int jj = 0; jj < np; ++jj) {
-        const int j = k + jj;
-        for (int it = tid; it < u.cnt * NS4; it += 256) {
-            const int p = fdiv(a.dns4, it), g = it - p * NS4;
-            uint32_t acc = 0;
-            for (int i = 0; i < k; ++i) {
-                const uint32_t* t = tab + (i * np + jj) * 8;
-                if (!t[5]) continue;
-                const int r = p + H - (j - i);
-                acc ^= gf_mul4x(t, *reinterpret_cast<const uint32_t*>(planes + (i * ROWS + r) * SP + 4 * g));
-            }
-            uint8_t* o = out + p * CW + 4 * g * n + j;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (4 * g + e < S) o[e * n] = static_cast<uint8_t>(acc >> (8 * e));
-        }
-    }
-    __syncthreads();
-    if (tid < u.cnt) a.cw_len[u.row0 + tid] = last_nonzero_end(out + tid * CW, CW);  // FEC_Encoder.cpp:55-60
-    burst_flush(gcw, smem, ao, u.cnt * CW, tid, 256);
-    if (u.lead != 0) return;
-    // the burst's last min(total, W) windows into the ring
-    const int m = min(u.total, W), t0 = u.total - m;
-    const bool far = u.total > u.cnt;  // they lie (partly) behind this chunk: their payload rows again
-    const uint8_t* g1 = a.payload + (u.row0 + t0) * L;
-    const int raw1 = a.off_io + static_cast<int>(reinterpret_cast<uintptr_t>(g1) & 3);
-    if (far) {
-        __syncthreads();
-        burst_stage(smem, a.off_io, g1, m * L, tid, 256);
-        __syncthreads();
-    }
-    for (int idx = tid; idx < m * nq; idx += 256) {
-        const int tt = fdiv(dnq, idx), q = idx - tt * nq, t = t0 + tt;
-        const int ln = far ? (a.len ? min(max(a.len[u.row0 + t], 0), L) : L) : 0;
-        uint8_t v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int b = min(4 * q + e, SK - 1);
-            if (far) {
-                v[e] = b == 0 ? static_cast<uint8_t>(ln >> 8)
-                              : b == 1 ? static_cast<uint8_t>(ln & 0xff) : (b - 2 < ln ? smem[raw1 + tt * L + b - 2] : 0);
-            } else {
-                const int s = fdiv(a.dk, b), i = b - s * k;
-                v[e] = planes[(i * ROWS + t + H) * SP + s];
-            }
-        }
-        uint8_t* dst = a.win + (static_cast<int64_t>(u.id) * W + (u.seq0 + t) % W) * SK + 4 * q;
-        if ((SK & 3) == 0) {
-            *reinterpret_cast<uint32_t*>(dst) = uint32_t(v[0]) | (uint32_t(v[1]) << 8) | (uint32_t(v[2]) << 16) |
-                                                (uint32_t(v[3]) << 24);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (4 * q + e < SK) dst[e] = v[e];
-        }
-    }
-}
+struct BurstEncRows {        // an encode call's row arrays (R rows)
+    const uint8_t* payload;  // rows of L bytes
+    const int32_t* len;      // payload sizes (null: all L)
+    uint8_t* cw;             // rows of the group's codeword stride
+    int32_t* cw_len;
+};
+struct BurstDecRows {        // a decode call's row arrays (R rows)
+    const uint8_t* cw_in;    // rows of the group's codeword stride (rows of erased packets are not read)
+    const uint8_t* flags;    // a byte each: fate | kRowClamp | kRowErased
+    const uint8_t* coefs;    // the recovered rows' k x n blocks
+    uint8_t* out;            // rows of L bytes
+    int32_t* out_len;
+};
 
-// One workgroup per chunk.  LDS: the GF tables; the codewords of the chunk's packets and of the
-// T+k-1 in front of them (each row at its own dword phase); the recovered rows' coefficient
-// blocks; the chunk's output rows.
-__global__ __launch_bounds__(256) void fec_streams_decode_burst_kernel(BurstDecArgs a) {
-    extern __shared__ __align__(16) uint8_t smem[];
-    const int tid = threadIdx.x;
-    const BurstUnit u = a.units[blockIdx.x];
-    const int L = a.L, k = a.k, n = a.n, CW = a.CW, CWS = a.CWS, CWD = a.CWD, LW = a.LW, T = a.T;
-    const int HR = a.HR, ROWS = a.ROWS, TP = a.TP, kn = k * n;
-    uint8_t* gexp = smem;
-    uint8_t* glog = smem + 512;
-    int* rowoff = reinterpret_cast<int*>(smem + a.off_meta);  // [ROWS] LDS offset of the row's byte 0; -1: none
-    int* cord = rowoff + ROWS;                                // [TP] coefficient block of a recovered row
-    int* lnS = cord + TP;                                     // [TP] output length
-    int* cpS = lnS + TP;                                      // [TP] payload bytes copied
-    uint8_t* fl = reinterpret_cast<uint8_t*>(cpS + TP);       // [TP] row flags
-    for (int i = tid; i < 768; i += 256) smem[i] = a.gf[i];
-    const int hb = min(HR, u.lead);
-    uint8_t* ringb = a.ring + static_cast<int64_t>(u.id) * kRR * CW;
-    // row r = packet seq0 + r - HR; its codeword's address (null: missing, or before the stream)
-    for (int r = tid; r < ROWS; r += 256) {
-        const int p = r - HR;
-        const uint8_t* g = nullptr;
-        if (p < u.cnt) {
-            if (p >= -hb) {
-                const uint8_t f = a.flags[u.row0 + p];
-                if (p >= 0) fl[p] = f;
-                if (!(f & kRowErased)) g = a.cw_in + (u.row0 + p) * CW;
-            } else if (u.seq0 + p >= 0) {
-                g = ringb + ((u.seq0 + p) % kRR) * CW;
-            }
-        }
-        rowoff[r] = g ? a.off_rows + r * CWS + static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3) : -1;
-    }
-    __syncthreads();
-    auto row_src = [&](int r) -> const uint8_t* {
-        if (rowoff[r] < 0) return nullptr;
-        const int p = r - HR;
-        return p >= -hb ? a.cw_in + (u.row0 + p) * CW : ringb + ((u.seq0 + p) % kRR) * CW;
-    };
-    if (tid < u.cnt) {
-        int c = 0;
-        for (int j = 0; j < tid; ++j) c += (fl[j] & 3) == kRecovered;
-        cord[tid] = c;
-    }
-    int nrec = 0;
-    for (int j = 0; j < u.cnt; ++j) nrec += (fl[j] & 3) == kRecovered;
-    const uint8_t* gco = a.coefs + static_cast<int64_t>(u.coef0) * kn;
-    if (nrec) burst_stage(smem, a.off_coef, gco, nrec * kn, tid, 256);
-    const uint8_t* coefs = smem + a.off_coef + static_cast<int>(reinterpret_cast<uintptr_t>(gco) & 3);
-    // dword w of row r (the row's bytes from its dword phase on): batches of loads in flight
-    auto stage_rows = [&](int nrows, auto src_of) {
-        for (int base = 0; base < nrows * CWD; base += 256 * 4) {
-            uint32_t v[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int idx = base + q * 256 + tid;
-                v[q] = 0;
-                if (idx >= nrows * CWD) continue;
-                const int r = fdiv(a.dcwd, idx), w = idx - r * CWD;
-                const uint8_t* g = src_of(r);
-                if (!g) continue;
-                const int ph = static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
-                const int lo = 4 * w - ph;  // the dword's first byte in the row
-                if (lo >= CW) continue;
-                if (lo >= 0 && lo + 4 <= CW) {
-                    v[q] = *reinterpret_cast<const uint32_t*>(g + lo);
-                } else {
-                    for (int e = 0; e < 4; ++e)
-                        if (lo + e >= 0 && lo + e < CW) v[q] |= uint32_t(g[lo + e]) << (8 * e);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int idx = base + q * 256 + tid;
-                if (idx >= nrows * CWD) continue;
-                const int r = fdiv(a.dcwd, idx), w = idx - r * CWD;
-                *reinterpret_cast<uint32_t*>(smem + a.off_rows + r * CWS + 4 * w) = v[q];
-            }
-        }
-    };
-    stage_rows(HR + u.cnt, row_src);
-    __syncthreads();
-    // window byte h of output row j (packet x = seq0 + j - T = row j + k - 1)
-    auto byte_at = [&](int j, int h) -> uint8_t {
-        const int s = fdiv(a.dk, h), i = h - s * k;
-        if ((fl[j] & 3) == kCopy) {
-            const int ro = rowoff[j + k - 1];
-            return ro < 0 ? 0 : smem[ro + s * n + i];
-        }
-        const uint8_t* coef = coefs + cord[j] * kn + i * n;
-        uint8_t acc = 0;
-        for (int q = 0; q < n; ++q) {  // symbol q of packet x - i + q
-            const uint8_t c = coef[q];
-            const int r = j + k - 1 - i + q;
-            if (!c || r > j + HR) continue;
-            const int ro = rowoff[r];
-            if (ro >= 0) acc ^= gmul(gexp, glog, c, smem[ro + s * n + q]);
-        }
-        return acc;
-    };
-    if (tid < u.cnt) {  // header bytes first: they bound the copy
-        const int fate = fl[tid] & 3;
-        int ln = 0;
-        if (fate == kCopy || fate == kRecovered) {
-            const int hdr = byte_at(tid, 0) * 256 + byte_at(tid, 1);
-            ln = (fl[tid] & kRowClamp) ? min(hdr, L) : hdr;
-        }
-        lnS[tid] = ln;
-        cpS[tid] = min(ln, L);
-        a.out_len[u.row0 + tid] = ln;
-    }
-    __syncthreads();
-    uint8_t* gout = a.out + u.row0 * L;
-    const int ao = a.off_out + static_cast<int>(reinterpret_cast<uintptr_t>(gout) & 3);
-    for (int it = tid; it < u.cnt * LW; it += 256) {
-        const int j = fdiv(a.dlw, it), w = it - j * LW;
-        const int cp = cpS[j];
-        uint8_t* o = smem + ao + j * L + 4 * w;
-        if ((fl[j] & 3) == kCopy) {  // systematic bytes of the packet's own codeword
-            const int ro = rowoff[j + k - 1];
-            int s = fdiv(a.dk, 4 * w + 2), i = 4 * w + 2 - s * k;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int b = 4 * w + e;
-                if (b < L) o[e] = (b < cp && ro >= 0) ? smem[ro + s * n + i] : 0;
-                if (++i == k) i = 0, ++s;
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int b = 4 * w + e;
-                if (b < L) o[e] = b < cp ? byte_at(j, b + 2) : 0;
-            }
-        }
-    }
-    __syncthreads();
-    burst_flush(gout, smem, ao, u.cnt * L, tid, 256);
-    if (u.lead != 0) return;
-    // the burst's last min(total, T + k) codewords into the ring (missing ones leave their slot as it is)
-    const int m = min(u.total, T + k), t0 = u.total - m;
-    int slot0 = HR + t0;  // LDS row of burst row t0
-    if (u.total > u.cnt) {  // they lie (partly) behind this chunk: staged again, rows 0 .. m-1
-        slot0 = 0;
-        for (int r = tid; r < m; r += 256) {
-            const uint8_t* g = a.cw_in + (u.row0 + t0 + r) * CW;
-            rowoff[r] = (a.flags[u.row0 + t0 + r] & kRowErased)
-                            ? -1 : a.off_rows + r * CWS + static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
-        }
-        __syncthreads();
-        auto tail_src = [&](int r) -> const uint8_t* {
-            return rowoff[r] < 0 ? nullptr : a.cw_in + (u.row0 + t0 + r) * CW;
-        };
-        stage_rows(m, tail_src);
-        __syncthreads();
-    }
-    for (int tt = tid >> 6; tt < m; tt += 4) {
-        const int ro = rowoff[slot0 + tt];
-        if (ro >= 0) burst_flush(ringb + ((u.seq0 + t0 + tt) % kRR) * CW, smem, ro, CW, tid & 63, 64);
-    }
-}
-
-// ---- mixed groups: a code per stream, every chunk with its own geometry ------------------------
-// The burst kernels' work with the geometry taken from a per-code table in device memory instead of
-// the kernel arguments: a chunk's unit names its code, and since the code is the same for the whole
-// workgroup (read through readfirstlane) the table entry arrives by scalar loads, once, before the
-// kernel's first store.  The group's rows and slots have one stride for all codes: codeword rows
-// cwr = the largest CW (a stream's codeword is the first CW bytes of its row, its own code's CW;
-// encode zeroes the rest, decode never reads it), a window slot of `slot` bytes and a ring slot of
-// kRR x cwr bytes per stream, in which a stream uses its own W, SK and CW.
-// A stream that changes code (fec_streams_set_code) starts again at seq 0 in the same slots with
-// nothing cleared: both kernels read a window / ring row only for a packet seq >= 0 of the stream's
-// current life (the `u.seq0 + p >= 0` tests below), and every such window row was written in this
-// life; a ring row of a missing packet keeps older bytes, which meet only zero coefficients, as in
-// the burst kernels.
-
-struct MixedUnit {   // one chunk = one workgroup
-    int64_t row0;    // its first row in the call's row arrays
-    int64_t seq0;    // that row's sequence number in its stream
-    int64_t coef;    // decode: byte offset of the chunk's first coefficient block (k x n of its own code each)
-    int32_t id;
-    int32_t cnt;     // rows of the chunk (<= the code's TP)
-    int32_t lead;    // rows of the burst in front of the chunk (0: the first chunk)
-    int32_t total;   // rows of the burst
-    int32_t code;
-    int32_t pad;
+struct BurstEncArgs {  // one-code group: the geometry in the arguments
+    BurstEncRows rows;
+    const BurstUnit* units;
+    uint8_t* win;      // [streams][W][SK] window ring
+    BurstEncGeom g;
+};
+struct BurstDecArgs {
+    BurstDecRows rows;
+    const BurstUnit* units;
+    uint8_t* ring;     // [streams][kRR][CW]
+    BurstDecGeom g;
 };
 
 struct MixedEncCode {  // table entry of one code
-    BurstEncArgs g;    // burst_enc_lds' geometry at the code's chunk size, and ptab (no other pointer is used)
+    BurstEncGeom g;    // at the code's chunk size
     int64_t slot;      // bytes of a stream's window slot
     int cwr;           // the group's codeword row stride
     int pad;
 };
 struct MixedDecCode {
-    BurstDecArgs g;    // burst_dec_lds' geometry at the code's chunk size, and gf
+    BurstDecGeom g;
     int cwr;
     int pad;
 };
-
-struct MixedEncArgs {
-    const uint8_t* payload;  // R rows of L bytes
-    const int32_t* len;      // R payload sizes (null: all L)
-    const MixedUnit* units;
+struct MixedEncArgs {  // mixed group: the geometry from codes[unit.code]
+    BurstEncRows rows;
+    const BurstUnit* units;
+    uint8_t* win;      // [streams][slot]
     const MixedEncCode* codes;
-    uint8_t* win;            // [streams][slot]
-    uint8_t* cw;             // R rows of cwr bytes
-    int32_t* cw_len;
 };
-
 struct MixedDecArgs {
-    const uint8_t* cw_in;    // R rows of cwr bytes (rows of erased packets are not read)
-    const MixedUnit* units;
+    BurstDecRows rows;
+    const BurstUnit* units;
+    uint8_t* ring;     // [streams][kRR][cwr]
     const MixedDecCode* codes;
-    const uint8_t* flags;    // R bytes: fate | kRowClamp | kRowErased
-    const uint8_t* coefs;    // the recovered rows' k x n blocks
-    uint8_t* ring;           // [streams][kRR][cwr]
-    uint8_t* out;            // R rows of L bytes
-    int32_t* out_len;
 };
 
 // Zero global g[0, nb): whole dwords with dword stores.
@@ -742,21 +438,25 @@ __device__ __forceinline__ void burst_zero(uint8_t* g, int nb, int t, int nt) {
     if (t < nb - tail0) g[tail0 + t] = 0;
 }
 
-// fec_streams_encode_burst_kernel's chunk, its geometry from the table.
-__global__ __launch_bounds__(256) void fec_streams_encode_mixed_kernel(MixedEncArgs a) {
+// One workgroup's chunk u of an encode call.  slot: the stream's windows ([W][SK]); CWR: the codeword
+// row stride (a one-code kernel passes g.CW itself, and the zero fill below folds away).
+// LDS: the parity tables; the windows of the chunk's packets and of the n-1 in front of them as
+// position planes [i][row][sub-stream] (the four sub-streams of one gf_mul4x sit in one dword); the
+// chunk's payload rows, later its codewords; the ring's rows.
+__device__ __forceinline__ void burst_encode_chunk(const BurstEncGeom& g, const BurstUnit& u, const BurstEncRows& a,
+                                                   uint8_t* slot, int CWR) {
     extern __shared__ __align__(16) uint8_t smem[];
     const int tid = threadIdx.x;
-    const MixedUnit u = a.units[blockIdx.x];
-    const MixedEncCode c = a.codes[__builtin_amdgcn_readfirstlane(u.code)];
-    const BurstEncArgs& g = c.g;
     const int L = g.L, k = g.k, n = g.n, S = g.S, SP = g.SP, NS4 = g.NS4, CW = g.CW, SK = g.SK, SKS = g.SKS;
-    const int W = g.W, ROWS = g.ROWS, np = n - k, H = n - 1, CWR = c.cwr;
+    const int W = g.W, ROWS = g.ROWS, np = n - k, H = n - 1;
     uint32_t* tab = reinterpret_cast<uint32_t*>(smem);
     uint8_t* planes = smem + g.off_planes;
     int* lens = reinterpret_cast<int*>(smem + g.off_len);  // per row: payload size; -1 no packet; -2 ring row
-    for (int i = tid; i < k * np * 8; i += 256) tab[i] = g.ptab[i];
+    // the tables are device memory: said here, because a pointer read from the mixed kernels' table is
+    // generic to the compiler, which then loads through it with flat instructions and leaves this loop rolled
+    const auto* ptab = (const __attribute__((address_space(1))) uint32_t*)g.ptab;
+    for (int i = tid; i < k * np * 8; i += 256) tab[i] = ptab[i];
     const int hb = min(H, u.lead);  // rows in front of the chunk that lie in the burst
-    uint8_t* slot = a.win + static_cast<int64_t>(u.id) * c.slot;
     // row r = packet seq0 + r - H; a ring row only for a packet of the stream's current life (seq >= 0)
     for (int r = tid; r < ROWS; r += 256) {
         const int p = r - H;
@@ -869,7 +569,7 @@ __global__ __launch_bounds__(256) void fec_streams_encode_mixed_kernel(MixedEncA
                 v[e] = planes[(i * ROWS + t + H) * SP + s];
             }
         }
-        uint8_t* dst = slot + ((u.seq0 + t) % W) * SK + 4 * q;  // slot: a multiple of 16 bytes
+        uint8_t* dst = slot + ((u.seq0 + t) % W) * SK + 4 * q;  // dword aligned whenever SK is a multiple of 4
         if ((SK & 3) == 0) {
             *reinterpret_cast<uint32_t*>(dst) = uint32_t(v[0]) | (uint32_t(v[1]) << 8) | (uint32_t(v[2]) << 16) |
                                                 (uint32_t(v[3]) << 24);
@@ -881,15 +581,16 @@ __global__ __launch_bounds__(256) void fec_streams_encode_mixed_kernel(MixedEncA
     }
 }
 
-// fec_streams_decode_burst_kernel's chunk, its geometry from the table.
-__global__ __launch_bounds__(256) void fec_streams_decode_mixed_kernel(MixedDecArgs a) {
+// One workgroup's chunk u of a decode call.  ring: the stream's kRR ring rows; CWR: the row stride of
+// the ring and of the call's codeword rows.
+// LDS: the GF tables; the codewords of the chunk's packets and of the T+k-1 in front of them (each
+// row at its own dword phase); the recovered rows' coefficient blocks; the chunk's output rows.
+__device__ __forceinline__ void burst_decode_chunk(const BurstDecGeom& g, const BurstUnit& u, const BurstDecRows& a,
+                                                   uint8_t* ring, int CWR) {
     extern __shared__ __align__(16) uint8_t smem[];
     const int tid = threadIdx.x;
-    const MixedUnit u = a.units[blockIdx.x];
-    const MixedDecCode c = a.codes[__builtin_amdgcn_readfirstlane(u.code)];
-    const BurstDecArgs& g = c.g;
     const int L = g.L, k = g.k, n = g.n, CW = g.CW, CWS = g.CWS, CWD = g.CWD, LW = g.LW, T = g.T;
-    const int HR = g.HR, ROWS = g.ROWS, TP = g.TP, kn = k * n, CWR = c.cwr;
+    const int HR = g.HR, ROWS = g.ROWS, TP = g.TP, kn = k * n;
     uint8_t* gexp = smem;
     uint8_t* glog = smem + 512;
     int* rowoff = reinterpret_cast<int*>(smem + g.off_meta);  // [ROWS] LDS offset of the row's byte 0; -1: none
@@ -899,7 +600,6 @@ __global__ __launch_bounds__(256) void fec_streams_decode_mixed_kernel(MixedDecA
     uint8_t* fl = reinterpret_cast<uint8_t*>(cpS + TP);       // [TP] row flags
     for (int i = tid; i < 768; i += 256) smem[i] = g.gf[i];
     const int hb = min(HR, u.lead);
-    uint8_t* ringb = a.ring + static_cast<int64_t>(u.id) * kRR * CWR;
     // row r = packet seq0 + r - HR; its codeword's address (null: missing, or before the stream's
     // current life: a ring row is read only for seq >= 0)
     for (int r = tid; r < ROWS; r += 256) {
@@ -911,7 +611,7 @@ __global__ __launch_bounds__(256) void fec_streams_decode_mixed_kernel(MixedDecA
                 if (p >= 0) fl[p] = f;
                 if (!(f & kRowErased)) gr = a.cw_in + (u.row0 + p) * CWR;
             } else if (u.seq0 + p >= 0) {
-                gr = ringb + ((u.seq0 + p) % kRR) * CWR;
+                gr = ring + ((u.seq0 + p) % kRR) * CWR;
             }
         }
         rowoff[r] = gr ? g.off_rows + r * CWS + static_cast<int>(reinterpret_cast<uintptr_t>(gr) & 3) : -1;
@@ -920,12 +620,12 @@ __global__ __launch_bounds__(256) void fec_streams_decode_mixed_kernel(MixedDecA
     auto row_src = [&](int r) -> const uint8_t* {
         if (rowoff[r] < 0) return nullptr;
         const int p = r - HR;
-        return p >= -hb ? a.cw_in + (u.row0 + p) * CWR : ringb + ((u.seq0 + p) % kRR) * CWR;
+        return p >= -hb ? a.cw_in + (u.row0 + p) * CWR : ring + ((u.seq0 + p) % kRR) * CWR;
     };
     if (tid < u.cnt) {
-        int cnt = 0;
-        for (int j = 0; j < tid; ++j) cnt += (fl[j] & 3) == kRecovered;
-        cord[tid] = cnt;
+        int c = 0;
+        for (int j = 0; j < tid; ++j) c += (fl[j] & 3) == kRecovered;
+        cord[tid] = c;
     }
     int nrec = 0;
     for (int j = 0; j < u.cnt; ++j) nrec += (fl[j] & 3) == kRecovered;
@@ -975,11 +675,11 @@ __global__ __launch_bounds__(256) void fec_streams_decode_mixed_kernel(MixedDecA
         const uint8_t* coef = coefs + cord[j] * kn + i * n;
         uint8_t acc = 0;
         for (int q = 0; q < n; ++q) {  // symbol q of packet x - i + q
-            const uint8_t cf = coef[q];
+            const uint8_t c = coef[q];
             const int r = j + k - 1 - i + q;
-            if (!cf || r > j + HR) continue;
+            if (!c || r > j + HR) continue;
             const int ro = rowoff[r];
-            if (ro >= 0) acc ^= gmul(gexp, glog, cf, smem[ro + s * n + q]);
+            if (ro >= 0) acc ^= gmul(gexp, glog, c, smem[ro + s * n + q]);
         }
         return acc;
     };
@@ -1040,8 +740,30 @@ __global__ __launch_bounds__(256) void fec_streams_decode_mixed_kernel(MixedDecA
     }
     for (int tt = tid >> 6; tt < m; tt += 4) {
         const int ro = rowoff[slot0 + tt];
-        if (ro >= 0) burst_flush(ringb + ((u.seq0 + t0 + tt) % kRR) * CWR, smem, ro, CW, tid & 63, 64);
+        if (ro >= 0) burst_flush(ring + ((u.seq0 + t0 + tt) % kRR) * CWR, smem, ro, CW, tid & 63, 64);
     }
+}
+
+__global__ __launch_bounds__(256) void fec_streams_encode_burst_kernel(BurstEncArgs a) {
+    const BurstUnit u = a.units[blockIdx.x];
+    burst_encode_chunk(a.g, u, a.rows, a.win + static_cast<int64_t>(u.id) * a.g.W * a.g.SK, a.g.CW);
+}
+
+__global__ __launch_bounds__(256) void fec_streams_decode_burst_kernel(BurstDecArgs a) {
+    const BurstUnit u = a.units[blockIdx.x];
+    burst_decode_chunk(a.g, u, a.rows, a.ring + static_cast<int64_t>(u.id) * kRR * a.g.CW, a.g.CW);
+}
+
+__global__ __launch_bounds__(256) void fec_streams_encode_mixed_kernel(MixedEncArgs a) {
+    const BurstUnit u = a.units[blockIdx.x];
+    const MixedEncCode c = a.codes[__builtin_amdgcn_readfirstlane(u.code)];
+    burst_encode_chunk(c.g, u, a.rows, a.win + static_cast<int64_t>(u.id) * c.slot, c.cwr);
+}
+
+__global__ __launch_bounds__(256) void fec_streams_decode_mixed_kernel(MixedDecArgs a) {
+    const BurstUnit u = a.units[blockIdx.x];
+    const MixedDecCode c = a.codes[__builtin_amdgcn_readfirstlane(u.code)];
+    burst_decode_chunk(c.g, u, a.rows, a.ring + static_cast<int64_t>(u.id) * kRR * c.cwr, c.cwr);
 }
 
 }  // namespace
@@ -1281,8 +1003,8 @@ int check_counts(const int32_t* counts, int M, int64_t* R, int* maxc) {
     return FEC_OK;
 }
 
-// LDS carve-up of fec_streams_encode_burst_kernel for chunks of tp packets (fills a's geometry); its bytes
-int burst_enc_lds(const fec::Geometry& g, int tp, fec::BurstEncArgs* a) {
+// LDS carve-up of burst_encode_chunk for chunks of tp packets: fills the geometry but ptab; returns its bytes
+int burst_enc_lds(const fec::Geometry& g, int tp, fec::BurstEncGeom* a) {
     const int np = g.n - g.k, H = g.n - 1, SK = g.S * g.k;
     a->L = g.L, a->k = g.k, a->n = g.n, a->S = g.S, a->CW = g.CW, a->SK = SK;
     a->NS4 = (g.S + 3) / 4;
@@ -1306,7 +1028,7 @@ int burst_enc_lds(const fec::Geometry& g, int tp, fec::BurstEncArgs* a) {
     return static_cast<int>(std::min<size_t>(off, 1u << 30));
 }
 
-int burst_dec_lds(const fec::Geometry& g, int tp, fec::BurstDecArgs* a) {
+int burst_dec_lds(const fec::Geometry& g, int tp, fec::BurstDecGeom* a) {
     a->L = g.L, a->k = g.k, a->n = g.n, a->CW = g.CW, a->T = g.T;
     a->CWD = (g.CW + 6) >> 2;
     a->CWS = 4 * a->CWD;
@@ -1332,8 +1054,8 @@ int burst_dec_lds(const fec::Geometry& g, int tp, fec::BurstDecArgs* a) {
 // Packets per chunk for a call whose longest burst has maxc packets: at most kBurstTP (or maxc), at
 // least `front` (the packets a chunk needs in front of it, so that only a burst's first chunk reads
 // the ring), and within kBurstLds.  0: this geometry does not fit.
-template <class Args, class F>
-int burst_chunk(const fec::Geometry& g, int maxc, int front, F lds_of, Args* a, int* lds) {
+template <class Geom, class F>
+int burst_chunk(const fec::Geometry& g, int maxc, int front, F lds_of, Geom* a, int* lds) {
     if (g.S * g.k > 16384 || g.CW > 16384) return 0;
     const int lo = std::max(1, front);
     for (int tp = std::max(lo, std::min(maxc, kBurstTP)); tp >= lo; --tp) {
@@ -1343,27 +1065,20 @@ int burst_chunk(const fec::Geometry& g, int maxc, int front, F lds_of, Args* a, 
     return 0;
 }
 
-// The call's chunks: bursts in row order, each cut every tp rows.  seq: packets of each stream so far.
-int64_t burst_units(const int32_t* counts, int M, int tp) {
-    int64_t nu = 0;
-    for (int m = 0; m < M; ++m) nu += (counts[m] + tp - 1) / tp;
-    return nu;
-}
-void burst_fill_units(fec::BurstUnit* u, const int32_t* ids, const int32_t* counts, int m0, int m1, int64_t row,
-                      int tp, const std::vector<int64_t>& seq) {
-    for (int m = m0; m < m1; ++m) {
-        for (int lead = 0; lead < counts[m]; lead += tp, ++u) {
-            u->row0 = row + lead;
-            u->seq0 = seq[ids[m]] + lead;
-            u->id = ids[m];
-            u->cnt = std::min(tp, counts[m] - lead);
-            u->lead = lead;
-            u->total = counts[m];
-            u->coef0 = 0;
-            u->pad = 0;
-        }
-        row += counts[m];
+// The chunks of one burst of `count` rows, cut every tp rows; returns the unit after them.
+fec::BurstUnit* burst_fill_units(fec::BurstUnit* u, int id, int code, int count, int64_t row, int tp, int64_t seq) {
+    for (int lead = 0; lead < count; lead += tp, ++u) {
+        u->row0 = row + lead;
+        u->seq0 = seq + lead;
+        u->coef = 0;
+        u->id = id;
+        u->cnt = std::min(tp, count - lead);
+        u->lead = lead;
+        u->total = count;
+        u->code = code;
+        u->pad = 0;
     }
+    return u;
 }
 
 // The symbolic half of a burst for one stream: packets seq0 .. seq0 + count - 1 with erasure flags
@@ -1433,8 +1148,8 @@ constexpr int kMaxCodes = 64;
 struct CodeFit {
     fec::Geometry g;
     int enc_tp = 0, enc_lds = 0, dec_tp = 0, dec_lds = 0;
-    fec::BurstEncArgs enc;
-    fec::BurstDecArgs dec;
+    fec::BurstEncGeom enc;
+    fec::BurstDecGeom dec;
 };
 int mixed_code_fit(int L, const int32_t* tbn, CodeFit* f) {
     try {
@@ -1445,82 +1160,88 @@ int mixed_code_fit(int L, const int32_t* tbn, CodeFit* f) {
     const fec::Geometry& g = f->g;
     if (g.L > 1500 || g.B < g.N || g.n > fec::kMaxN - 1) return FEC_ERR_ARG;
     if (g.T + g.k > fec::kRR || g.k > 16 || g.k * g.n > 16 * 32) return FEC_ERR_ARG;
-    f->enc = fec::BurstEncArgs{};
-    f->dec = fec::BurstDecArgs{};
+    f->enc = fec::BurstEncGeom{};
+    f->dec = fec::BurstDecGeom{};
     f->enc_tp = burst_chunk(g, kBurstTP, g.n - 1, burst_enc_lds, &f->enc, &f->enc_lds);
     f->dec_tp = burst_chunk(g, kBurstTP, g.T + g.k - 1, burst_dec_lds, &f->dec, &f->dec_lds);
     return f->enc_tp && f->dec_tp ? FEC_OK : FEC_ERR_ARG;
 }
 
-// The chunks of one burst of `count` rows, cut every tp rows; returns the unit after them.
-fec::MixedUnit* mixed_fill_units(fec::MixedUnit* u, int id, int code, int count, int64_t row, int tp, int64_t seq) {
-    for (int lead = 0; lead < count; lead += tp, ++u) {
-        u->row0 = row + lead;
-        u->seq0 = seq + lead;
-        u->coef = 0;
-        u->id = id;
-        u->cnt = std::min(tp, count - lead);
-        u->lead = lead;
-        u->total = count;
-        u->code = code;
-        u->pad = 0;
-    }
-    return u;
-}
+// ---- chunk calls: bursts of any group, and a mixed group's one-packet calls ----------------------
 
-// A mixed call's shape: counts (null: all 1) >= 1, ids distinct; R rows, nu chunks, and the largest
-// chunk LDS among the codes present in this call.
-int mixed_call_shape(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, bool enc, int64_t* R,
-                     int64_t* nu, int* lds) {
-    int maxc = 1;
-    *R = M;
-    if (counts)
-        if (int st = check_counts(counts, M, R, &maxc)) return st;
-    if (int st = check_ids(h, ids, M)) return st;
-    *nu = 0;
+// What the chunks of one stream follow in a call: its code's index in the mixed kernels' table, the
+// chunk size and LDS of this direction, T and k x n.
+struct ChunkCode {
+    int code, tp, lds, T, kn;
+};
+// A one-code group: `one` for every stream, its chunk cut for the call's largest burst (burst_chunk).
+// A mixed group: the stream's own code, its chunk fixed at create.
+inline ChunkCode chunk_code(const fec_streams* h, bool enc, const ChunkCode& one, int id) {
+    if (h->codes.empty()) return one;
+    const int code = h->code_of[id];
+    const fec_streams::Code& c = h->codes[code];
+    return ChunkCode{code, enc ? c.enc_tp : c.dec_tp, enc ? c.enc_lds : c.dec_lds, c.g.T, c.g.k * c.g.n};
+}
+// The call's chunks (counts null: one packet per stream), and the largest chunk LDS among its streams' codes.
+int64_t chunk_count(const fec_streams* h, bool enc, const ChunkCode& one, const int32_t* ids, const int32_t* counts,
+                    int M, int* lds) {
+    int64_t nu = 0;
     *lds = 0;
     for (int m = 0; m < M; ++m) {
-        const fec_streams::Code& c = h->codes[h->code_of[ids[m]]];
-        const int tp = enc ? c.enc_tp : c.dec_tp;
-        *nu += ((counts ? counts[m] : 1) + tp - 1) / tp;
-        *lds = std::max(*lds, enc ? c.enc_lds : c.dec_lds);
+        const ChunkCode c = chunk_code(h, enc, one, ids[m]);
+        nu += ((counts ? counts[m] : 1) + c.tp - 1) / c.tp;
+        *lds = std::max(*lds, c.lds);
     }
-    return *nu > INT32_MAX ? FEC_ERR_ARG : FEC_OK;
+    return nu;
 }
 
-// fec_streams_encode / fec_streams_encode_burst on a mixed group (counts null: one packet per stream).
-int mixed_encode(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, const uint8_t* d_payload,
-                 const int32_t* d_payload_len, uint8_t* d_codeword, int32_t* d_codeword_len, hipStream_t s) {
-    int64_t R = 0, nu = 0;
+// The encode half of a chunk call; counts (null: all 1) are checked, the largest is maxc.
+int encode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, int maxc, const uint8_t* d_payload,
+                  const int32_t* d_payload_len, uint8_t* d_codeword, int32_t* d_codeword_len, hipStream_t s) {
+    if (int st = check_ids(h, ids, M)) return st;
+    const bool mixed = !h->codes.empty();
+    fec::BurstEncArgs a1;  // a one-code group's arguments: its geometry
+    ChunkCode one{};
+    if (!mixed) {
+        one = ChunkCode{0, 0, 0, h->g.T, h->g.k * h->g.n};
+        one.tp = burst_chunk(h->g, maxc, h->g.n - 1, burst_enc_lds, &a1.g, &one.lds);
+        if (one.tp == 0) return FEC_ERR_ARG;
+    }
     int lds = 0;
-    if (int st = mixed_call_shape(h, ids, counts, M, true, &R, &nu, &lds)) return st;
-    static int lds_raised = 0;
-    if (int st = burst_lds_allow(reinterpret_cast<const void*>(fec::fec_streams_encode_mixed_kernel), lds, &lds_raised))
-        return st;
+    const int64_t nu = chunk_count(h, true, one, ids, counts, M, &lds);
+    if (nu > INT32_MAX) return FEC_ERR_ARG;
+    static int lds_raised[2] = {0, 0};  // per kernel
+    const void* kernel = mixed ? reinterpret_cast<const void*>(fec::fec_streams_encode_mixed_kernel)
+                               : reinterpret_cast<const void*>(fec::fec_streams_encode_burst_kernel);
+    if (int st = burst_lds_allow(kernel, lds, &lds_raised[mixed])) return st;
     int b = 0;
     if (int st = stage_free(h, s, &b)) return st;
-    const size_t bytes = static_cast<size_t>(nu) * sizeof(fec::MixedUnit);
+    const size_t bytes = static_cast<size_t>(nu) * sizeof(fec::BurstUnit);
     if (int st = stage_reserve(h, b, bytes)) {
         h->poisoned = true;  // the buffer may be gone
         return st;
     }
-    fec::MixedUnit* u = static_cast<fec::MixedUnit*>(h->h_stage[b]);
+    fec::BurstUnit* u = static_cast<fec::BurstUnit*>(h->h_stage[b]);
     int64_t row = 0;
     for (int m = 0; m < M; ++m) {
-        const int id = ids[m], code = h->code_of[id], cnt = counts ? counts[m] : 1;
-        u = mixed_fill_units(u, id, code, cnt, row, h->codes[code].enc_tp, h->enc_seq[id]);
+        const int id = ids[m], cnt = counts ? counts[m] : 1;
+        const ChunkCode c = chunk_code(h, true, one, id);
+        u = burst_fill_units(u, id, c.code, cnt, row, c.tp, h->enc_seq[id]);
         row += cnt;
     }
     if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
-    fec::MixedEncArgs a;
-    a.payload = d_payload;
-    a.len = d_payload_len;
-    a.units = static_cast<const fec::MixedUnit*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
-    a.codes = h->d_enc_codes;
-    a.win = h->d_win;
-    a.cw = d_codeword;
-    a.cw_len = d_codeword_len;
-    hipLaunchKernelGGL(fec::fec_streams_encode_mixed_kernel, dim3(static_cast<unsigned>(nu)), dim3(256), lds, s, a);
+    const fec::BurstEncRows rows{d_payload, d_payload_len, d_codeword, d_codeword_len};
+    const fec::BurstUnit* du = static_cast<const fec::BurstUnit*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
+    const dim3 grid(static_cast<unsigned>(nu));
+    if (mixed) {
+        const fec::MixedEncArgs a{rows, du, h->d_win, h->d_enc_codes};
+        hipLaunchKernelGGL(fec::fec_streams_encode_mixed_kernel, grid, dim3(256), lds, s, a);
+    } else {
+        fec::CodecView v;
+        fec::codec_view(h->codec, &v);
+        a1.rows = rows, a1.units = du, a1.win = h->d_win, a1.g.ptab = v.ptab;
+        hipLaunchKernelGGL(fec::fec_streams_encode_burst_kernel, grid, dim3(256), lds, s, a1);
+    }
     FS_TRY(hipGetLastError());
     FS_TRY(hipEventRecord(h->done, s));
     FS_TRY(hipEventRecord(h->staged[b], s));
@@ -1529,16 +1250,26 @@ int mixed_encode(fec_streams* h, const int32_t* ids, const int32_t* counts, int 
     return FEC_OK;
 }
 
-// fec_streams_decode / fec_streams_decode_burst on a mixed group (counts null: one packet per stream):
-// fec_streams_decode_burst's host side with each stream's own planner, T, k x n and chunk size.
-int mixed_decode(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, const uint8_t* erasure,
-                 const uint8_t* d_codeword, uint8_t* d_payload_out, int32_t* d_payload_len, hipStream_t s) {
-    int64_t R = 0, nu = 0;
+// The decode half of a chunk call; counts (null: all 1) are checked, their sum is R and the largest maxc.
+int decode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, int64_t R, int maxc,
+                  const uint8_t* erasure, const uint8_t* d_codeword, uint8_t* d_payload_out, int32_t* d_payload_len,
+                  hipStream_t s) {
+    if (int st = check_ids(h, ids, M)) return st;
+    const bool mixed = !h->codes.empty();
+    fec::BurstDecArgs a1;  // a one-code group's arguments: its geometry
+    ChunkCode one{};
+    if (!mixed) {
+        one = ChunkCode{0, 0, 0, h->g.T, h->g.k * h->g.n};
+        one.tp = burst_chunk(h->g, maxc, h->g.T + h->g.k - 1, burst_dec_lds, &a1.g, &one.lds);
+        if (one.tp == 0) return FEC_ERR_ARG;
+    }
     int lds = 0;
-    if (int st = mixed_call_shape(h, ids, counts, M, false, &R, &nu, &lds)) return st;
-    static int lds_raised = 0;
-    if (int st = burst_lds_allow(reinterpret_cast<const void*>(fec::fec_streams_decode_mixed_kernel), lds, &lds_raised))
-        return st;
+    const int64_t nu = chunk_count(h, false, one, ids, counts, M, &lds);
+    if (nu > INT32_MAX) return FEC_ERR_ARG;
+    static int lds_raised[2] = {0, 0};  // per kernel
+    const void* kernel = mixed ? reinterpret_cast<const void*>(fec::fec_streams_decode_mixed_kernel)
+                               : reinterpret_cast<const void*>(fec::fec_streams_decode_burst_kernel);
+    if (int st = burst_lds_allow(kernel, lds, &lds_raised[mixed])) return st;
     int b = 0;
     if (int st = stage_free(h, s, &b)) return st;
     // The symbolic decoders advance before the launch: a failure from here on leaves the host planners
@@ -1551,15 +1282,16 @@ int mixed_decode(fec_streams* h, const int32_t* ids, const int32_t* counts, int 
     try {
         // streams are independent: contiguous parts of them, one per thread; a part's recovered rows
         // keep their coefficient blocks in row order
+        // (the pool calls every one of its parts: a call with fewer streams than parts leaves some empty)
         const int np = (h->pool && R >= 2 * kPoolMinItems) ? h->pool->parts() : 1;
         std::vector<int64_t> row_at(M + 1, 0), unit_at(M + 1, 0);
         for (int m = 0; m < M; ++m) {
-            const int cnt = counts ? counts[m] : 1, tp = h->codes[h->code_of[ids[m]]].dec_tp;
+            const int cnt = counts ? counts[m] : 1, tp = chunk_code(h, false, one, ids[m]).tp;
             row_at[m + 1] = row_at[m] + cnt;
             unit_at[m + 1] = unit_at[m] + (cnt + tp - 1) / tp;
         }
         std::vector<uint8_t> flags(static_cast<size_t>(R));
-        std::vector<fec::MixedUnit> units(static_cast<size_t>(nu));
+        std::vector<fec::BurstUnit> units(static_cast<size_t>(nu));
         std::vector<std::vector<uint8_t>> coefs(np);
         std::atomic<bool> failed{false};
         auto part = [&](int p) {
@@ -1569,18 +1301,17 @@ int mixed_decode(fec_streams* h, const int32_t* ids, const int32_t* counts, int 
                 const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
                 int64_t cbytes = 0;  // coefficient bytes of this part's chunks so far
                 for (int m = m0; m < m1; ++m) {
-                    const int id = ids[m], code = h->code_of[id], cnt = counts ? counts[m] : 1;
-                    const fec_streams::Code& c = h->codes[code];
-                    const int kn = c.g.k * c.g.n;
-                    mixed_fill_units(units.data() + unit_at[m], id, code, cnt, row_at[m], c.dec_tp, h->dec_seq[id]);
-                    plan_burst_rows(*h->planners[id], c.g.T, kn, h->dec_seq[id], erasure + row_at[m], cnt,
+                    const int id = ids[m], cnt = counts ? counts[m] : 1;
+                    const ChunkCode c = chunk_code(h, false, one, id);
+                    burst_fill_units(units.data() + unit_at[m], id, c.code, cnt, row_at[m], c.tp, h->dec_seq[id]);
+                    plan_burst_rows(*h->planners[id], c.T, c.kn, h->dec_seq[id], erasure + row_at[m], cnt,
                                     flags.data() + row_at[m], coefs[p]);
                     h->dec_seq[id] += cnt;
                     for (int64_t ui = unit_at[m]; ui < unit_at[m + 1]; ++ui) {
-                        fec::MixedUnit& u = units[ui];
+                        fec::BurstUnit& u = units[ui];
                         u.coef = cbytes;
                         for (int j = 0; j < u.cnt; ++j)
-                            if ((flags[u.row0 + j] & 3) == fec::kRecovered) cbytes += kn;
+                            if ((flags[u.row0 + j] & 3) == fec::kRecovered) cbytes += c.kn;
                     }
                 }
             } catch (...) {
@@ -1593,7 +1324,7 @@ int mixed_decode(fec_streams* h, const int32_t* ids, const int32_t* counts, int 
             part(0);
         if (failed.load()) return FEC_ERR_ARG;
         // staging: units | row flags | coefficient blocks
-        const size_t off_flags = align16(static_cast<size_t>(nu) * sizeof(fec::MixedUnit));
+        const size_t off_flags = align16(static_cast<size_t>(nu) * sizeof(fec::BurstUnit));
         const size_t off_coef = align16(off_flags + static_cast<size_t>(R));
         size_t ncoef = 0;
         for (const auto& c : coefs) ncoef += c.size();
@@ -1609,20 +1340,22 @@ int mixed_decode(fec_streams* h, const int32_t* ids, const int32_t* counts, int 
             if (!coefs[p].empty()) std::memcpy(hs + off_coef + cbase, coefs[p].data(), coefs[p].size());
             cbase += coefs[p].size();
         }
-        std::memcpy(hs, units.data(), units.size() * sizeof(fec::MixedUnit));
+        std::memcpy(hs, units.data(), units.size() * sizeof(fec::BurstUnit));
         std::memcpy(hs + off_flags, flags.data(), flags.size());
         if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
         const uint8_t* rec = static_cast<const uint8_t*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
-        fec::MixedDecArgs a;
-        a.cw_in = d_codeword;
-        a.units = reinterpret_cast<const fec::MixedUnit*>(rec);
-        a.codes = h->d_dec_codes;
-        a.flags = rec + off_flags;
-        a.coefs = rec + off_coef;
-        a.ring = h->d_ring;
-        a.out = d_payload_out;
-        a.out_len = d_payload_len;
-        hipLaunchKernelGGL(fec::fec_streams_decode_mixed_kernel, dim3(static_cast<unsigned>(nu)), dim3(256), lds, s, a);
+        const fec::BurstDecRows rows{d_codeword, rec + off_flags, rec + off_coef, d_payload_out, d_payload_len};
+        const fec::BurstUnit* du = reinterpret_cast<const fec::BurstUnit*>(rec);
+        const dim3 grid(static_cast<unsigned>(nu));
+        if (mixed) {
+            const fec::MixedDecArgs a{rows, du, h->d_ring, h->d_dec_codes};
+            hipLaunchKernelGGL(fec::fec_streams_decode_mixed_kernel, grid, dim3(256), lds, s, a);
+        } else {
+            fec::CodecView v;
+            fec::codec_view(h->codec, &v);
+            a1.rows = rows, a1.units = du, a1.ring = h->d_ring, a1.g.gf = v.gf;
+            hipLaunchKernelGGL(fec::fec_streams_decode_burst_kernel, grid, dim3(256), lds, s, a1);
+        }
         FS_TRY(hipGetLastError());
         FS_TRY(hipEventRecord(h->done, s));
         FS_TRY(hipEventRecord(h->staged[b], s));
@@ -1736,9 +1469,9 @@ int fec_streams_encode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
     if (!h || M < 0 || M > h->nstreams || (M > 0 && (!ids || !d_payload || !d_codeword || !d_codeword_len)))
         return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
-    if (!h->codes.empty())
-        return mixed_encode(h, ids, nullptr, M, d_payload, d_payload_len, d_codeword, d_codeword_len,
-                            static_cast<hipStream_t>(stream));
+    if (!h->codes.empty())  // a mixed group: chunks of one packet
+        return encode_chunks(h, ids, nullptr, M, 1, d_payload, d_payload_len, d_codeword, d_codeword_len,
+                             static_cast<hipStream_t>(stream));
     if (int st = check_ids(h, ids, M)) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int b = 0;
@@ -1792,9 +1525,9 @@ int fec_streams_decode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
                                                      !d_payload_len)))
         return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
-    if (!h->codes.empty())
-        return mixed_decode(h, ids, nullptr, M, erasure, d_codeword, d_payload_out, d_payload_len,
-                            static_cast<hipStream_t>(stream));
+    if (!h->codes.empty())  // a mixed group: chunks of one packet
+        return decode_chunks(h, ids, nullptr, M, M, 1, erasure, d_codeword, d_payload_out, d_payload_len,
+                             static_cast<hipStream_t>(stream));
     static const bool dbg = std::getenv("FEC_STREAMS_DEBUG") != nullptr;  // per-phase host times
     const auto t0 = std::chrono::steady_clock::now();
     if (int st = check_ids(h, ids, M)) return st;
@@ -1897,50 +1630,13 @@ int fec_streams_encode_burst(fec_streams* h, const int32_t* ids, const int32_t* 
         (M > 0 && (!ids || !counts || !d_payload || !d_codeword || !d_codeword_len)))
         return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
-    if (!h->codes.empty())
-        return mixed_encode(h, ids, counts, M, d_payload, d_payload_len, d_codeword, d_codeword_len,
-                            static_cast<hipStream_t>(stream));
     int64_t R = 0;
     int maxc = 0;
     if (int st = check_counts(counts, M, &R, &maxc)) return st;
-    if (maxc == 1)  // one packet per stream: the one-packet kernel
+    if (h->codes.empty() && maxc == 1)  // one packet per stream of a one-code group: the one-packet kernel
         return fec_streams_encode(h, ids, M, d_payload, d_payload_len, d_codeword, d_codeword_len, stream);
-    if (int st = check_ids(h, ids, M)) return st;
-    fec::BurstEncArgs a;
-    int lds = 0;
-    const int tp = burst_chunk(h->g, maxc, h->g.n - 1, burst_enc_lds, &a, &lds);
-    if (tp == 0) return FEC_ERR_ARG;
-    const int64_t nu = burst_units(counts, M, tp);
-    if (nu > INT32_MAX) return FEC_ERR_ARG;
-    static int lds_raised = 0;
-    if (int st = burst_lds_allow(reinterpret_cast<const void*>(fec::fec_streams_encode_burst_kernel), lds, &lds_raised))
-        return st;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int b = 0;
-    if (int st = stage_free(h, s, &b)) return st;
-    const size_t bytes = static_cast<size_t>(nu) * sizeof(fec::BurstUnit);
-    if (int st = stage_reserve(h, b, bytes)) {
-        h->poisoned = true;  // the buffer may be gone
-        return st;
-    }
-    burst_fill_units(static_cast<fec::BurstUnit*>(h->h_stage[b]), ids, counts, 0, M, 0, tp, h->enc_seq);
-    if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
-    fec::CodecView v;
-    fec::codec_view(h->codec, &v);
-    a.payload = d_payload;
-    a.len = d_payload_len;
-    a.units = static_cast<const fec::BurstUnit*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
-    a.win = h->d_win;
-    a.cw = d_codeword;
-    a.cw_len = d_codeword_len;
-    a.ptab = v.ptab;
-    hipLaunchKernelGGL(fec::fec_streams_encode_burst_kernel, dim3(static_cast<unsigned>(nu)), dim3(256), lds, s, a);
-    FS_TRY(hipGetLastError());
-    FS_TRY(hipEventRecord(h->done, s));
-    FS_TRY(hipEventRecord(h->staged[b], s));
-    h->buf = (b + 1) % fec_streams::kStageBufs;
-    for (int m = 0; m < M; ++m) h->enc_seq[ids[m]] += counts[m];
-    return FEC_OK;
+    return encode_chunks(h, ids, counts, M, maxc, d_payload, d_payload_len, d_codeword, d_codeword_len,
+                         static_cast<hipStream_t>(stream));
 }
 
 int fec_streams_decode_burst(fec_streams* h, const int32_t* ids, const int32_t* counts, int M,
@@ -1950,121 +1646,13 @@ int fec_streams_decode_burst(fec_streams* h, const int32_t* ids, const int32_t* 
         (M > 0 && (!ids || !counts || !erasure || !d_codeword || !d_payload_out || !d_payload_len)))
         return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
-    if (!h->codes.empty())
-        return mixed_decode(h, ids, counts, M, erasure, d_codeword, d_payload_out, d_payload_len,
-                            static_cast<hipStream_t>(stream));
     int64_t R = 0;
     int maxc = 0;
     if (int st = check_counts(counts, M, &R, &maxc)) return st;
-    if (maxc == 1)  // one packet per stream: the one-packet kernel
+    if (h->codes.empty() && maxc == 1)  // one packet per stream of a one-code group: the one-packet kernel
         return fec_streams_decode(h, ids, M, erasure, d_codeword, d_payload_out, d_payload_len, stream);
-    if (int st = check_ids(h, ids, M)) return st;
-    const fec::Geometry& g = h->g;
-    fec::BurstDecArgs a;
-    int lds = 0;
-    const int tp = burst_chunk(g, maxc, g.T + g.k - 1, burst_dec_lds, &a, &lds);
-    if (tp == 0) return FEC_ERR_ARG;
-    const int64_t nu = burst_units(counts, M, tp);
-    if (nu > INT32_MAX) return FEC_ERR_ARG;
-    static int lds_raised = 0;
-    if (int st = burst_lds_allow(reinterpret_cast<const void*>(fec::fec_streams_decode_burst_kernel), lds, &lds_raised))
-        return st;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int b = 0;
-    if (int st = stage_free(h, s, &b)) return st;
-    const int kn = g.k * g.n;
-    // The symbolic decoders advance before the launch: a failure from here on leaves the host planners
-    // ahead of the device rings, and the group refuses every later call.
-    struct Poison {
-        fec_streams* h;
-        bool armed = true;
-        ~Poison() { if (armed) h->poisoned = true; }
-    } poison{h};
-    try {
-        // streams are independent: contiguous parts of them, one per thread; a part's recovered rows
-        // keep their coefficient blocks in row order
-        // (the pool calls every one of its parts: a call with fewer streams than parts leaves some empty)
-        const int np = (h->pool && R >= 2 * kPoolMinItems) ? h->pool->parts() : 1;
-        std::vector<int64_t> row_at(M + 1, 0), unit_at(M + 1, 0);
-        for (int m = 0; m < M; ++m) {
-            row_at[m + 1] = row_at[m] + counts[m];
-            unit_at[m + 1] = unit_at[m] + (counts[m] + tp - 1) / tp;
-        }
-        std::vector<uint8_t> flags(static_cast<size_t>(R));
-        std::vector<fec::BurstUnit> units(static_cast<size_t>(nu));
-        std::vector<std::vector<uint8_t>> coefs(np);
-        std::atomic<bool> failed{false};
-        auto part = [&](int p) {
-            if (p < 0 || p >= np) return;
-            try {
-                const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
-                const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
-                burst_fill_units(units.data() + unit_at[m0], ids, counts, m0, m1, row_at[m0], tp, h->dec_seq);
-                int32_t nrec = 0;
-                for (int m = m0; m < m1; ++m) {
-                    const int id = ids[m];
-                    plan_burst_rows(*h->planners[id], g.T, kn, h->dec_seq[id], erasure + row_at[m], counts[m],
-                                         flags.data() + row_at[m], coefs[p]);
-                    h->dec_seq[id] += counts[m];
-                    for (int64_t ui = unit_at[m]; ui < unit_at[m + 1]; ++ui) {
-                        fec::BurstUnit& u = units[ui];
-                        u.coef0 = nrec;
-                        for (int j = 0; j < u.cnt; ++j) nrec += (flags[u.row0 + j] & 3) == fec::kRecovered;
-                    }
-                }
-            } catch (...) {
-                failed.store(true);
-            }
-        };
-        if (np > 1)
-            h->pool->run(part);
-        else
-            part(0);
-        if (failed.load()) return FEC_ERR_ARG;
-        // staging: units | row flags | coefficient blocks
-        const size_t off_flags = align16(static_cast<size_t>(nu) * sizeof(fec::BurstUnit));
-        const size_t off_coef = align16(off_flags + static_cast<size_t>(R));
-        size_t ncoef = 0;
-        for (const auto& c : coefs) ncoef += c.size();
-        if (ncoef / kn > INT32_MAX) return FEC_ERR_ARG;
-        const size_t bytes = off_coef + ncoef + 16;
-        if (int st = stage_reserve(h, b, bytes)) return st;
-        uint8_t* hs = static_cast<uint8_t*>(h->h_stage[b]);
-        size_t cbase = 0;
-        for (int p = 0; p < np; ++p) {  // a part's blocks follow those of the parts before it
-            const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
-            const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
-            if (cbase)
-                for (int64_t ui = unit_at[m0]; ui < unit_at[m1]; ++ui) units[ui].coef0 += static_cast<int32_t>(cbase / kn);
-            if (!coefs[p].empty()) std::memcpy(hs + off_coef + cbase, coefs[p].data(), coefs[p].size());
-            cbase += coefs[p].size();
-        }
-        std::memcpy(hs, units.data(), units.size() * sizeof(fec::BurstUnit));
-        std::memcpy(hs + off_flags, flags.data(), flags.size());
-        if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
-        const uint8_t* rec = static_cast<const uint8_t*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
-        fec::CodecView v;
-        fec::codec_view(h->codec, &v);
-        a.cw_in = d_codeword;
-        a.units = reinterpret_cast<const fec::BurstUnit*>(rec);
-        a.flags = rec + off_flags;
-        a.coefs = rec + off_coef;
-        a.ring = h->d_ring;
-        a.gf = v.gf;
-        a.out = d_payload_out;
-        a.out_len = d_payload_len;
-        hipLaunchKernelGGL(fec::fec_streams_decode_burst_kernel, dim3(static_cast<unsigned>(nu)), dim3(256), lds, s, a);
-        FS_TRY(hipGetLastError());
-        FS_TRY(hipEventRecord(h->done, s));
-        FS_TRY(hipEventRecord(h->staged[b], s));
-        h->buf = (b + 1) % fec_streams::kStageBufs;
-        poison.armed = false;
-        return FEC_OK;
-    } catch (const std::bad_alloc&) {
-        return FEC_ERR_NOMEM;
-    } catch (...) {
-        return FEC_ERR_ARG;
-    }
+    return decode_chunks(h, ids, counts, M, R, maxc, erasure, d_codeword, d_payload_out, d_payload_len,
+                         static_cast<hipStream_t>(stream));
 }
 
 int fec_streams_plan_burst_host(int max_payload, int T, int B, int N, const uint8_t* erasure,
@@ -2168,7 +1756,7 @@ int fec_streams_create_mixed(int max_payload, const int32_t* tuples, int ncodes,
         FS_TRY(hipMemcpy(h->d_dec_codes, dt.data(), dt.size() * sizeof(dt[0]), hipMemcpyHostToDevice));
         const size_t wb = static_cast<size_t>(nstreams) * h->win_slot;
         const size_t rb = static_cast<size_t>(nstreams) * fec::kRR * h->cw_stride;
-        const size_t stage = static_cast<size_t>(nstreams) * (sizeof(fec::MixedUnit) + 1 + kn_max + 16) + 64;
+        const size_t stage = static_cast<size_t>(nstreams) * (sizeof(fec::BurstUnit) + 1 + kn_max + 16) + 64;
         if (int st = group_state_init(h.get(), wb, rb, stage)) return st;
         *out = h.release();
         return FEC_OK;
@@ -2204,7 +1792,7 @@ int fec_streams_set_code(fec_streams* h, int id, int code) {
         return FEC_ERR_ARG;
     try {
         // host work only: the kernels read a window or ring row only for a packet seq >= 0 of the
-        // stream's current life, so the slot's old bytes are never seen (see the mixed kernels)
+        // stream's current life, so the slot's old bytes are never seen (see "bursts")
         std::unique_ptr<fec::StreamPlanner> pl(
             h->codes.empty() ? new fec::StreamPlanner(h->g, h->rules.get())
                              : new fec::StreamPlanner(h->codes[code].g, h->codes[code].rules.get()));
