@@ -330,8 +330,10 @@ __device__ __forceinline__ void tile_walk(const EncTileArgs& a, uint8_t* smem) {
             }
         }
         if (has_len) {
-            const int r = row0 + a.history + lane;
-            const bool ok = wv == 0 && lane < R && r >= 0;
+            // wave wv brings the lengths of tile rows 64*wv .. 64*wv+63 (R reaches 256 at small L)
+            const int rl = wv * 64 + lane;
+            const int r = row0 + a.history + rl;
+            const bool ok = rl < R && r >= 0;
             dma4(rl4, static_cast<uint32_t>(ok ? r * 4 : 0x7fffffff), lds_len + (it & 1) * 1024 + wv * 256);
             ++vm_issued;
         }

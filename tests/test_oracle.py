@@ -150,3 +150,71 @@ def test_decoder_created_midstream_and_startup_erasures():
         src = oracle.fill_payload(0, P, 300, 0x5EED)
         ok = r["out_len"] > 0
         assert (r["out_data"][ok] == src[ok]).all()
+
+
+# ---- payload sizes that are not whole dwords ---------------------------------------------------
+# The cases tests/test_gpu_buffers.py runs on the GPU; pinned here first, on the CPU alone.
+ODD_TUPLES = [(10, 3, 3), (10, 5, 2), (10, 10, 10), (10, 9, 1), (4, 6, 2), (10, 0, 0)]
+ODD_SIZES = [1, 2, 3, 5, 37, 299, 301]
+ODD_P = 400  # outputs; the stream has T more packets
+ODD_LOSSY = [(10, 3, 3), (10, 5, 2), (10, 9, 1), (4, 6, 2)]  # tuples the pattern must cost a packet
+
+
+def odd_size_pattern(T, B, P=ODD_P):
+    """P + T flags, fixed seed: about 8 % i.i.d. loss, erasures among the first T+2 packets, one
+    burst of B+1 packets (longer than the code's burst tolerance), and an episode that runs into
+    the batch end (erased outputs P-3, P-2 and erasures inside the last T packets after them)."""
+    rng = np.random.default_rng(0x0DD5)
+    pat = (rng.random(P + T) < 0.08).astype(np.uint8)
+    pat[[1, T + 1]] = 1
+    pat[150:150 + B + 1] = 1
+    pat[P - 3:P - 1] = 1
+    pat[P + T - 4:P + T - 1] = 1
+    return pat
+
+
+@pytest.mark.parametrize("L", ODD_SIZES)
+@pytest.mark.parametrize("tbn", ODD_TUPLES)
+def test_round_trip_at_odd_payload_sizes(tbn, L):
+    """Encode -> erase -> decode at payload sizes with L % 4 != 0: every delivered packet is its
+    source payload, the lost set is the symbolic host planner's, and the pattern makes every code
+    with parity recover a packet and the weaker ones lose one."""
+    import fec_erasure_code_unit_test_relay_amd as fec
+    T, B, N = tbn
+    P = ODD_P
+    pat = odd_size_pattern(T, B)
+    r = oracle.run_stream(L, T, B, N, P, pat, want_data=True)
+    src = oracle.fill_payload(0, P, L, 0x5EED)
+    ok = r["out_len"] > 0
+    assert (r["out_len"][ok] == L).all()
+    assert (r["out_data"][ok] == src[ok]).all()
+    assert (r["out_data"][~ok] == 0).all()
+    assert r["lost"] == int((~ok).sum())
+    assert (pat[:P][~ok] == 1).all()  # only erased packets are lost
+    assert ((fec.plan_host(L, T, B, N, pat) == 3) == ~ok).all()
+    if B > 0:
+        assert int((ok & (pat[:P] == 1)).sum()) >= 1  # a recovered packet
+    if tbn in ODD_LOSSY:
+        assert int((~ok).sum()) >= 1
+
+
+@pytest.mark.parametrize("L", ODD_SIZES)
+@pytest.mark.parametrize("tbn", ODD_TUPLES)
+def test_closed_form_encoder_at_odd_payload_sizes(tbn, L):
+    T, B, N = tbn
+    k, n, S, CW = oracle.geometry(L, T, B, N)
+    P = 120
+    rng = np.random.default_rng(L + sum(tbn))
+    payload = oracle.fill_payload(0, P, L, 7)
+    lens = rng.integers(0, L + 1, size=P)
+    lens[:n] = L
+    lens[n:n + 3] = [0, 1, L]
+    enc = oracle.Encoder(L, T, B, N)
+    ref = np.zeros((P, CW), dtype=np.uint8)
+    wire = np.zeros(P, dtype=np.int64)
+    for t in range(P):
+        ref[t], wire[t] = enc.onTransmit(payload[t], int(lens[t]), t)
+    got = closed_form_encode(oracle.gen_G(T, B, N), payload, lens, k, n, S, L)
+    assert (got == ref).all()
+    nz = [np.flatnonzero(row) for row in ref]
+    assert all(wire[t] == (nz[t][-1] + 1 if nz[t].size else 0) for t in range(P))
