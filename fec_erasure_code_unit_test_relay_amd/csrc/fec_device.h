@@ -159,6 +159,18 @@ __device__ __forceinline__ void burst_flush(uint8_t* g, const uint8_t* smem, int
     if (t < nb - tail0) g[tail0 + t] = smem[off + tail0 + t];
 }
 
+// Zero global g[0, nb): whole dwords with dword stores.
+__device__ __forceinline__ void burst_zero(uint8_t* g, int nb, int t, int nt) {
+    const int a = static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
+    const int head = min(nb, (4 - a) & 3);
+    const int nd = (nb - head) >> 2;
+    const int tail0 = head + 4 * nd;
+    uint32_t* gd = reinterpret_cast<uint32_t*>(g + head);
+    for (int w = t; w < nd; w += nt) gd[w] = 0;
+    if (t < head) g[t] = 0;
+    if (t < nb - tail0) g[tail0 + t] = 0;
+}
+
 // Diagnostic phase stamp (s_memtime, shader clock) of workgroup `wg`, slot `k` of 8; only when a
 // stamp buffer is given.  Stamps never feed an output.
 __device__ __forceinline__ void phase_stamp(uint64_t* stamps, int wg, int k) {

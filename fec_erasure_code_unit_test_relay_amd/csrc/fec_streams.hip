@@ -426,18 +426,6 @@ struct MixedDecArgs {
     const MixedDecCode* codes;
 };
 
-// Zero global g[0, nb): whole dwords with dword stores.
-__device__ __forceinline__ void burst_zero(uint8_t* g, int nb, int t, int nt) {
-    const int a = static_cast<int>(reinterpret_cast<uintptr_t>(g) & 3);
-    const int head = min(nb, (4 - a) & 3);
-    const int nd = (nb - head) >> 2;
-    const int tail0 = head + 4 * nd;
-    uint32_t* gd = reinterpret_cast<uint32_t*>(g + head);
-    for (int w = t; w < nd; w += nt) gd[w] = 0;
-    if (t < head) g[t] = 0;
-    if (t < nb - tail0) g[tail0 + t] = 0;
-}
-
 // One workgroup's chunk u of an encode call.  slot: the stream's windows ([W][SK]); CWR: the codeword
 // row stride (a one-code kernel passes g.CW itself, and the zero fill below folds away).
 // LDS: the parity tables; the windows of the chunk's packets and of the n-1 in front of them as

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes
 
-from ._lib import check, lib
+from ._lib import FEC_ERR_ARG, FecError, check, lib
 
 
 def _ptr(t):
@@ -99,7 +99,58 @@ class RelayStreamGroup:
         v = [ctypes.c_int() for _ in range(7)]
         check(lib().fec_relay_streams_geometry(h, *[ctypes.byref(x) for x in v]), "fec_relay_streams_geometry")
         self.k, self.n1, self.n2, self.S, self.cw_bytes, self.frame_bytes, self.delay = (x.value for x in v)
+        self.out_bytes = self.S * self.k
         self.L, self.nstreams = max_payload, nstreams
+        self.codes = [(T1, N1, T2, N2)]
+        self.code_of = [0] * nstreams
+
+    @classmethod
+    def mixed(cls, max_payload: int, tuples, code_of) -> "RelayStreamGroup":
+        """A group whose stream s runs code tuples[code_of[s]] = (T1, N1, T2, N2)
+        (fec_relay_streams_create_mixed): one call serves streams of different codes in one launch per
+        side.  Every row array has one stride for the group: ``cw_bytes`` (the least codeword row),
+        ``frame_bytes`` and ``out_bytes`` are the largest of the codes'; a stream's codeword, frame or
+        output row is the first geometry(s)[...] bytes of its row, and the rest of a frame or output
+        row is zero.  k, n1, n2, S and delay are None: they are per stream."""
+        import numpy as np
+        if tuples is None or code_of is None:  # what the library answers to a null pointer
+            raise FecError(FEC_ERR_ARG, "fec_relay_streams_create_mixed")
+        tup = np.ascontiguousarray(tuples, dtype=np.int32).reshape(-1, 4)
+        cof = np.ascontiguousarray(code_of, dtype=np.int32).reshape(-1)
+        h = ctypes.c_void_p()
+        check(lib().fec_relay_streams_create_mixed(max_payload, tup.ctypes.data_as(ctypes.c_void_p), tup.shape[0],
+                                                   cof.ctypes.data_as(ctypes.c_void_p), cof.size, ctypes.byref(h)),
+              "fec_relay_streams_create_mixed")
+        self = cls.__new__(cls)
+        self._h = h
+        self.L, self.nstreams = max_payload, cof.size
+        v = [ctypes.c_int() for _ in range(4)]
+        check(lib().fec_relay_streams_codes(h, *[ctypes.byref(x) for x in v]), "fec_relay_streams_codes")
+        nc, self.cw_bytes, self.frame_bytes, self.out_bytes = (x.value for x in v)
+        assert nc == tup.shape[0]
+        self.codes = [tuple(int(x) for x in t) for t in tup]
+        self.code_of = [self.geometry(s)["code"] for s in range(cof.size)]
+        if nc == 1:
+            g = self.geometry(0)
+            self.k, self.n1, self.n2, self.S, self.delay = (g[x] for x in ("k", "n1", "n2", "S", "delay"))
+        else:
+            self.k = self.n1 = self.n2 = self.S = self.delay = None
+        return self
+
+    def geometry(self, stream_id: int) -> dict:
+        """Stream `stream_id`'s code index and that code's k, n1, n2, S, cw_bytes, frame_bytes,
+        out_bytes and delay."""
+        v = [ctypes.c_int() for _ in range(9)]
+        check(lib().fec_relay_streams_stream_geometry(self._h, stream_id, *[ctypes.byref(x) for x in v]),
+              "fec_relay_streams_stream_geometry")
+        return dict(zip(("code", "k", "n1", "n2", "S", "cw_bytes", "frame_bytes", "out_bytes", "delay"),
+                        (x.value for x in v)))
+
+    def set_code(self, stream_id: int, code: int) -> None:
+        """Stream `stream_id` becomes a fresh relay chain and a fresh destination chain of code `code`
+        (seq counters 0, no erasure behind it); the old chain's remaining outputs are never produced."""
+        check(lib().fec_relay_streams_set_code(self._h, stream_id, code), "fec_relay_streams_set_code")
+        self.code_of[stream_id] = code
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -154,15 +205,15 @@ class RelayStreamGroup:
 
     def destination(self, ids, counts, erasure, frames, out=None, flag=None):
         """symbol_wise_decode_1 + extract_data for the next counts[m] seqs of stream ids[m]: frames
-        [R, frame_bytes] on the GPU, erasure R host flags -> (data_with_header rows [R, S*k] (a row
+        [R, frame_bytes] on the GPU, erasure R host flags -> (data_with_header rows [R, out_bytes] (a row
         = source packet seq - delay of its stream), flags [R] uint8) on the GPU."""
         import torch
         ids, counts, er, R = self._rows(ids, counts, erasure)
         assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous()
         assert tuple(frames.shape) == (R, self.frame_bytes)
         if out is None:
-            out = torch.empty((R, self.S * self.k), dtype=torch.uint8, device=frames.device)
-        assert out.shape == (R, self.S * self.k) and out.is_contiguous() and out.dtype == torch.uint8
+            out = torch.empty((R, self.out_bytes), dtype=torch.uint8, device=frames.device)
+        assert out.shape == (R, self.out_bytes) and out.is_contiguous() and out.dtype == torch.uint8
         if flag is None:
             flag = torch.empty(R, dtype=torch.uint8, device=frames.device)
         assert flag.numel() >= R and flag.dtype == torch.uint8 and flag.is_contiguous()
@@ -188,6 +239,20 @@ def relay_streams_fit(relay: bool, max_payload: int, T1: int, N1: int, T2: int, 
     if st < 0:
         check(st, "fec_relay_streams_fit")
     return bool(st), tp.value, lds.value
+
+
+def relay_streams_mixed_fit(max_payload: int, tuples):
+    """Host only: per code of a mixed relay stream group (relay chunk, relay LDS bytes, destination
+    chunk, destination LDS bytes) as int32 arrays [ncodes] (fec_relay_streams_mixed_fit); FecError if a
+    tuple is refused or does not fit."""
+    import numpy as np
+    tup = np.ascontiguousarray(tuples, dtype=np.int32).reshape(-1, 4)
+    nc = tup.shape[0]
+    res = [np.zeros(max(nc, 1), dtype=np.int32) for _ in range(4)]
+    check(lib().fec_relay_streams_mixed_fit(max_payload, tup.ctypes.data_as(ctypes.c_void_p), nc,
+                                            *[r.ctypes.data_as(ctypes.c_void_p) for r in res]),
+          "fec_relay_streams_mixed_fit")
+    return tuple(r[:nc] for r in res)
 
 
 def relay_streams_plan_host(k: int, n: int, erasure, counts):

@@ -440,7 +440,53 @@ typedef struct fec_relay_streams fec_relay_streams;
 int fec_relay_streams_create(int max_payload, int T1, int N1, int T2, int N2, int nstreams,
                              fec_relay_streams **out);
 int fec_relay_streams_destroy(fec_relay_streams *group);
-/* cw_bytes = S*n1; delay = n1 + n2 - k - 1 (fec_swdf_geometry) */
+/* Mixed groups: every stream has its own (T1, N1, T2, N2), and one call serves streams of different
+ * codes in one launch per side -- the relay or destination node of many flows under variable rate,
+ * each on the code its own loss calls for.  tuples: ncodes x {T1, N1, T2, N2} (1 <= ncodes <= 64,
+ * equal tuples may repeat), code_of: nstreams indices into it.  FEC_ERR_ARG, nothing created: a tuple
+ * fec_relay_streams_create refuses at this max_payload, a tuple of which either side's smallest chunk
+ * does not fit a CU's LDS (fec_relay_streams_mixed_fit), a code index outside [0, ncodes), a null
+ * pointer.  The result is an ordinary group: fec_relay_streams_relay / _destination / _state /
+ * _destroy take it unchanged, with this row layout: each row array has one stride for the whole group
+ * (fec_relay_streams_codes).  d_cw rows: cw_stride >= the largest S*n1 of the group's codes; a
+ * stream's codeword is the first S*n1 bytes of its own code, the rest of the row is never read.
+ * d_frames rows: frame_stride = the largest frame size 2 + (S+1)*n2; the relay writes the stream's
+ * frame into the first bytes and zero behind it, the destination reads the stream's own frame bytes
+ * only.  d_out rows: out_stride = the largest S*k; the stream's data_with_header row, then zero.
+ * Per stream, the rows of all calls together equal fec_swdf_relay_batch / _destination_batch of its
+ * own tuple over its sequence from seq 0, whatever the cutting and whichever streams shared its
+ * calls.  Both sides run the table-driven kernels (fec_relay_streams.hip: the one-code kernels' chunk
+ * body with the code's geometry from a table in device memory); a call cuts a stream's burst into
+ * chunks of min(the call's longest burst, its code's chunk size) packets, and a launch takes the LDS
+ * of the largest chunk among the codes present in that call.  Device state per stream: a relay ring
+ * slot of max_c((n1_c+n2_c-2) S_c n1_c) bytes and a destination ring slot of max_c((n2_c-1) S_c n2_c). */
+int fec_relay_streams_create_mixed(int max_payload, const int32_t *tuples, int ncodes,
+                                   const int32_t *code_of, int nstreams, fec_relay_streams **out);
+/* The number of codes of a group (1 for fec_relay_streams_create's, whose strides are its own sizes)
+ * and its row strides: the least cw_stride, the frame rows' and the output rows'. */
+int fec_relay_streams_codes(const fec_relay_streams *group, int *ncodes, int *cw_bytes, int *frame_stride,
+                            int *out_stride);
+/* Stream `id`'s code index and that code's geometry: cw_bytes = S*n1, frame_bytes = 2 + (S+1)*n2,
+ * out_bytes = S*k, delay = n1 + n2 - k - 1 (any pointer may be NULL). */
+int fec_relay_streams_stream_geometry(const fec_relay_streams *group, int id, int *code, int *k, int *n1,
+                                      int *n2, int *S, int *cw_bytes, int *frame_bytes, int *out_bytes,
+                                      int *delay);
+/* Makes stream `id` a fresh relay chain and a fresh destination chain of code `code`, as the relay
+ * under variable rate starts a fresh fixed-rate chain per code instance: both seq counters go to 0
+ * and both flag registers to zero.  Host work only (calls already queued carry their own seqs; the
+ * kernels never read a stream's device state from before seq 0).  The old chain's remaining outputs
+ * are not produced: a caller that wants them through the double-coded seqs keeps the old stream id
+ * alive beside a second id.  On a group made by fec_relay_streams_create only code 0 is accepted,
+ * and resets the stream.  FEC_ERR_ARG (group unchanged): id or code out of range. */
+int fec_relay_streams_set_code(fec_relay_streams *group, int id, int code);
+/* Host only, no device call: per code the packets per chunk of a long burst and that chunk's LDS
+ * bytes on the relay and on the destination side (ncodes entries each), through the routines the
+ * calls use: entry c is fec_relay_streams_fit of tuple c.  FEC_ERR_ARG if any tuple is refused or
+ * does not fit, ncodes is outside [1, 64] or a pointer is null. */
+int fec_relay_streams_mixed_fit(int max_payload, const int32_t *tuples, int ncodes, int32_t *relay_chunk,
+                                int32_t *relay_lds, int32_t *dest_chunk, int32_t *dest_lds);
+/* cw_bytes = S*n1; delay = n1 + n2 - k - 1 (fec_swdf_geometry).  A group of one code; FEC_ERR_ARG
+ * for a group of several (fec_relay_streams_stream_geometry answers per stream). */
 int fec_relay_streams_geometry(const fec_relay_streams *group, int *k, int *n1, int *n2, int *S, int *cw_bytes,
                                int *frame_bytes, int *delay);
 int fec_relay_streams_relay(fec_relay_streams *group, const int32_t *ids, const int32_t *counts, int M,
