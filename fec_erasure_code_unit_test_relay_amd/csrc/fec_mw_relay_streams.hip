@@ -1,0 +1,745 @@
+// fec_mw_relay_streams.hip -- the message-wise decode-and-forward relay (RELAYING_TYPE 1) at fixed
+// rate for many independent flows of one (max_payload, T1,B1,N1, T2,B2,N2), one packet or a burst of
+// each named flow per call, hop-1 decode and hop-2 encode in one launch.
+//
+// Reference: per flow an FEC_Decoder of the hop-1 code feeding an FEC_Encoder of the hop-2 code, one
+// packet per call: FEC_Decoder::onReceive (FEC_Decoder.cpp:38-75: its own zero-padded copy of the
+// codeword :55-63, Decoder::decodeStream, Decoder.cpp:72-175) outputs message seq - T1, and
+// FEC_Encoder::onTransmit (FEC_Encoder.cpp:38-62: the window [len_hi, len_lo, payload, zero pad],
+// Encoder.cpp:73-95, the closed form :65-98, the trimmed size FEC_Encoder.cpp:55-60) codes it as its
+// packet number seq - T1.  A message the relay loses is forwarded as the empty message, so relay seq
+// and source seq stay equal (the driver's constant-transmission case).  This is the fixed-rate relay
+// of this library's per-packet contract, not the reference's adaptive session
+// (Variable_Rate_FEC_Decoder's stored-message vector, the 12-byte relay header, T2_ack).
+// The destination is an ordinary (T2,B2,N2) decoder: fec_streams_decode_burst of a fec_streams group
+// serves it, and there is no destination entry here.
+//
+// The rule is equivalence: per flow the rows of all calls together equal fec_streams_decode_burst over
+// the flow's hop-1 sequence, its first T1 rows dropped, then fec_streams_encode_burst over the rest
+// with lengths clipped to [0, L].  Both hops' lengths meet in one number: the decoder outputs hdr or
+// min(hdr, L) (the clamp rule, kRowClamp) and copies min(that, L) bytes; the encoder clips the length
+// to L; so the forwarded window is [min(hdr, L), the message's first min(hdr, L) bytes, zeros]
+// whichever way the decoder went, and no payload row has to exist in between.
+//
+// State in HBM per flow: the decoder's ring of the last kRR received hop-1 codewords (slot seq % kRR)
+// and the encoder's ring of the last n2-1 message windows (S2*k2 bytes, slot message % (n2-1)); on the
+// host the flow's symbolic decoder (fec::StreamPlanner) and its seq counter.
+//
+// A burst is cut into chunks of at most TP packets, one workgroup each.  A chunk of cnt rows decodes
+// its cnt messages and, unless it is the burst's first, the H2 = n2-1 messages in front of them
+// (another workgroup computes those, so they are decoded again from the call's own rows) into the
+// hop-2 position planes; then it encodes.  Each run of messages is one pass over its HR1 + count hop-1
+// codewords staged in LDS (HR1 = T1+k1-1): first the H2 in front (HR1 + H2 rows), then the chunk's own
+// (HR1 + cnt rows) over the same LDS -- HR1 + H2 + cnt rows at once do not fit a CU at 1 500-byte payloads.
+// Only a burst's first chunk has packets from before the call in front of it: it reads the codeword
+// ring and the window ring, and it alone writes them, after the barrier behind its staging, with the
+// burst's last min(total, T1+k1) received codewords and last min(messages, n2-1) windows -- decoded
+// again from the call's rows when they lie behind the chunk.  So no workgroup reads a ring row that
+// another workgroup of the launch writes; it takes TP >= HR1 + H2 whenever a burst has several chunks.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <memory>
+#include <new>
+#include <vector>
+
+#include "fec_amd.h"
+#include "fec_burst.h"
+#include "fec_device.h"
+#include "fec_host.h"
+#include "fec_kernels.h"
+#include "fec_status.h"
+
+namespace fec {
+namespace {
+
+constexpr int kMwTP = 32;            // packets per chunk, LDS permitting
+constexpr int kMwLds = 160 * 1024;   // a CU's LDS
+
+struct MwUnit {          // one chunk = one workgroup
+    int64_t row0;        // its first row in the call's row arrays
+    int64_t seq0;        // that row's hop-1 sequence number in its flow
+    int64_t coef;        // byte offset of the first coefficient block of the rows it decodes (recovered rows, in row order)
+    int64_t tail_coef;   // first chunk of a burst cut in several: the same for the burst's last rows
+    int32_t id;
+    int32_t cnt;         // rows of the chunk (<= TP)
+    int32_t lead;        // rows of the burst in front of the chunk (0: the first chunk)
+    int32_t total;       // rows of the burst
+};
+
+struct MwGeom {            // a chunk's geometry (mw_lds) and both codes' constants
+    const uint8_t* gf;     // exp[512], log[256]
+    const uint32_t* ptab;  // hop 2: [k2][n2-k2][8] gf_mul4x tables
+    int L, T1, k1, n1, CW1, CWS1, CWD1, HR1;
+    int k2, n2, S2, SP2, NS4, CW2, SK2, W2, H2;
+    int TP, PR, ROWS1, ROWS2;  // messages of a pass (max(TP, H2) where bursts are cut); staged codewords HR1 + PR; window rows H2 + TP
+    int off_gf, off_rows, off_coef, off_planes, off_meta;  // dynamic LDS carve-up (multiples of 16)
+    FastDiv dk1, dk2, dns4, dnq, dcwd;
+};
+
+struct MwArgs {
+    const uint8_t* cw_in;    // R rows of `stride` bytes (rows of erased packets are not read)
+    int64_t stride;
+    const uint8_t* flags;    // R bytes: fate | kRowClamp | kRowErased (plan_burst_rows)
+    const uint8_t* coefs;    // the recovered rows' k1 x n1 blocks
+    uint8_t* cw_out;         // R rows of CW2 bytes
+    int32_t* cw_len;
+    uint8_t* fate;           // R bytes (may be null)
+    const MwUnit* units;
+    uint8_t* ring1;          // [flows][kRR][CW1]
+    uint8_t* win2;           // [flows][W2][SK2]
+    MwGeom g;
+};
+
+// LDS: the hop-2 parity tables; the GF tables; a pass's staged hop-1 codewords, each row at its own
+// dword phase (later the chunk's hop-2 codewords); its recovered rows' coefficient blocks; the hop-2
+// windows as position planes [i][row][sub-stream] (window row r = message seq0 - T1 + r - H2); per
+// row offsets, flags and lengths.
+__global__ __launch_bounds__(256) void fec_mw_relay_streams_kernel(MwArgs a) {
+    extern __shared__ __align__(16) uint8_t smem[];
+    const MwGeom& g = a.g;
+    const MwUnit u = a.units[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int L = g.L, T1 = g.T1, k1 = g.k1, n1 = g.n1, CW1 = g.CW1, CWS1 = g.CWS1, CWD1 = g.CWD1, HR1 = g.HR1;
+    const int k2 = g.k2, n2 = g.n2, S2 = g.S2, SP2 = g.SP2, NS4 = g.NS4, CW2 = g.CW2, SK2 = g.SK2;
+    const int W2 = g.W2, H2 = g.H2, PR = g.PR, ROWS2 = g.ROWS2, np2 = n2 - k2, kn1 = k1 * n1;
+    uint32_t* tab = reinterpret_cast<uint32_t*>(smem);
+    const uint8_t* gexp = smem + g.off_gf;
+    const uint8_t* glog = gexp + 512;
+    uint8_t* planes = smem + g.off_planes;
+    int* rowoff = reinterpret_cast<int*>(smem + g.off_meta);  // [ROWS1] LDS offset of the codeword's byte 0; -1: none
+    int* cord = rowoff + g.ROWS1;                             // [PR] coefficient block of a recovered message
+    int* lnS = cord + PR;                                     // [PR] forwarded length min(hdr, L)
+    uint8_t* fl = reinterpret_cast<uint8_t*>(lnS + PR);       // [PR] row flags
+    uint8_t* ring1 = a.ring1 + static_cast<int64_t>(u.id) * kRR * CW1;
+    uint8_t* win2 = a.win2 + static_cast<int64_t>(u.id) * W2 * SK2;
+    const auto* ptab = (const __attribute__((address_space(1))) uint32_t*)g.ptab;
+    const auto* ggf = (const __attribute__((address_space(1))) uint8_t*)g.gf;
+    for (int i = tid; i < k2 * np2 * 8; i += 256) tab[i] = ptab[i];
+    for (int i = tid; i < 768; i += 256) smem[g.off_gf + i] = ggf[i];
+    const bool first = u.lead == 0;
+    const int nq = (SK2 + 3) >> 2;
+    const uint8_t* coefs = nullptr;
+
+    // hop-1 window byte h of a pass's output j (message sq + j - T1 = staged row j + k1 - 1); staged row R
+    // is packet sq + R - HR1
+    auto byte_at = [&](int j, int h) -> uint8_t {
+        const int s = fdiv(g.dk1, h), i = h - s * k1;
+        if ((fl[j] & 3) == kCopy) {
+            const int ro = rowoff[j + k1 - 1];
+            return ro < 0 ? 0 : smem[ro + s * n1 + i];
+        }
+        const uint8_t* coef = coefs + cord[j] * kn1 + i * n1;
+        uint8_t acc = 0;
+        for (int q = 0; q < n1; ++q) {  // symbol q of packet x - i + q
+            const uint8_t c = coef[q];
+            const int R = j + k1 - 1 - i + q;
+            if (!c || R > j + HR1) continue;
+            const int ro = rowoff[R];
+            if (ro >= 0) acc ^= gmul(gexp, glog, c, smem[ro + s * n1 + q]);
+        }
+        return acc;
+    };
+
+    // One pass: the messages of outputs j = 0 .. cnt-1 of the rows from call row rb (hop-1 seq sq) on,
+    // decoded into window rows prow0 + j of the planes; `front` rows of the burst lie in front of rb,
+    // older packets come from the ring.  Ends before the barrier that completes the planes; returns the
+    // recovered messages among them (the coefficient blocks it took from coef_off on).
+    auto decode_pass = [&](int64_t rb, int64_t sq, int cnt, int front, int64_t coef_off, int prow0) -> int {
+        const int R1 = HR1 + cnt;
+        auto call_row = [&](int R) { return R - HR1 >= -front; };
+        for (int R = tid; R < R1; R += 256) {
+            const int p = R - HR1;
+            const uint8_t* gr = nullptr;
+            if (call_row(R)) {
+                if (!(a.flags[rb + p] & kRowErased)) gr = a.cw_in + (rb + p) * a.stride;
+            } else if (sq + p >= 0) {
+                gr = ring1 + ((sq + p) % kRR) * CW1;
+            }
+            rowoff[R] = gr ? g.off_rows + R * CWS1 + static_cast<int>(reinterpret_cast<uintptr_t>(gr) & 3) : -1;
+        }
+        for (int j = tid; j < cnt; j += 256) fl[j] = a.flags[rb + j];
+        __syncthreads();
+        auto row_src = [&](int R) -> const uint8_t* {
+            if (rowoff[R] < 0) return nullptr;
+            const int p = R - HR1;
+            return call_row(R) ? a.cw_in + (rb + p) * a.stride : ring1 + ((sq + p) % kRR) * CW1;
+        };
+        if (tid < cnt) {
+            int c = 0;
+            for (int j = 0; j < tid; ++j) c += (fl[j] & 3) == kRecovered;
+            cord[tid] = c;
+        }
+        int nrec = 0;
+        for (int j = 0; j < cnt; ++j) nrec += (fl[j] & 3) == kRecovered;
+        const uint8_t* gco = a.coefs + coef_off;
+        if (nrec) burst_stage(smem, g.off_coef, gco, nrec * kn1, tid, 256);
+        coefs = smem + g.off_coef + static_cast<int>(reinterpret_cast<uintptr_t>(gco) & 3);
+        // dword w of staged row R (the row's first CW1 bytes from its dword phase on): batches of loads in flight
+        const int nw = R1 * CWD1;
+        for (int base = 0; base < nw; base += 256 * 4) {
+            uint32_t v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int idx = base + q * 256 + tid;
+                v[q] = 0;
+                if (idx >= nw) continue;
+                const int rr = fdiv(g.dcwd, idx), w = idx - rr * CWD1;
+                const uint8_t* gr = row_src(rr);
+                if (!gr) continue;
+                const int ph = static_cast<int>(reinterpret_cast<uintptr_t>(gr) & 3);
+                const int lo = 4 * w - ph;  // the dword's first byte in the row
+                if (lo >= CW1) continue;
+                if (lo >= 0 && lo + 4 <= CW1) {
+                    v[q] = *reinterpret_cast<const uint32_t*>(gr + lo);
+                } else {
+                    for (int e = 0; e < 4; ++e)
+                        if (lo + e >= 0 && lo + e < CW1) v[q] |= uint32_t(gr[lo + e]) << (8 * e);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int idx = base + q * 256 + tid;
+                if (idx >= nw) continue;
+                const int rr = fdiv(g.dcwd, idx), w = idx - rr * CWD1;
+                *reinterpret_cast<uint32_t*>(smem + g.off_rows + rr * CWS1 + 4 * w) = v[q];
+            }
+        }
+        __syncthreads();
+        if (tid < cnt) {  // header bytes first: they bound the copy (both hops' clips: min(hdr, L))
+            const int fate = fl[tid] & 3;
+            int ln = 0;
+            if (fate == kCopy || fate == kRecovered) ln = min(byte_at(tid, 0) * 256 + byte_at(tid, 1), L);
+            lnS[tid] = ln;
+        }
+        __syncthreads();
+        // window bytes 4q .. 4q+3 of message j: [len_hi, len_lo, payload, zero pad] (Encoder.cpp:75-83)
+        for (int idx = tid; idx < cnt * nq; idx += 256) {
+            const int j = fdiv(g.dnq, idx), q = idx - j * nq, r = prow0 + j;
+            const int ln = lnS[j];
+            const bool copy = (fl[j] & 3) == kCopy;
+            const int ro = rowoff[j + k1 - 1];
+            int s1 = fdiv(g.dk1, 4 * q), i1 = 4 * q - s1 * k1;
+            int s2 = fdiv(g.dk2, 4 * q), i2 = 4 * q - s2 * k2;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int b = 4 * q + e;
+                if (b < SK2) {
+                    uint8_t v = 0;
+                    if (b < 2)
+                        v = b == 0 ? static_cast<uint8_t>(ln >> 8) : static_cast<uint8_t>(ln & 0xff);
+                    else if (b < ln + 2)  // systematic byte of the message's own codeword, or through its block
+                        v = copy ? (ro >= 0 ? smem[ro + s1 * n1 + i1] : uint8_t(0)) : byte_at(j, b);
+                    planes[(i2 * ROWS2 + r) * SP2 + s2] = v;
+                }
+                if (++i1 == k1) i1 = 0, ++s1;
+                if (++i2 == k2) i2 = 0, ++s2;
+            }
+        }
+        return nrec;
+    };
+
+    // The burst's last received codewords and message windows into the rings, from the staged rows and
+    // the planes (from window row prow0 on) of the pass that decoded cntp messages ending with the burst's last row
+    // (first chunk only).
+    const int m1 = min(u.total, T1 + k1);
+    const int64_t early = T1 - u.seq0;  // rows of seq < T1: no message yet
+    const int nmsg = early <= 0 ? u.total : (early >= u.total ? 0 : u.total - static_cast<int>(early));
+    const int m2 = min(nmsg, H2);
+    auto write_rings = [&](int cntp, int prow0) {
+        for (int tt = tid >> 6; tt < m1; tt += 4) {  // missing ones leave their slot as it is
+            const int ro = rowoff[HR1 + cntp - m1 + tt];
+            if (ro >= 0) burst_flush(ring1 + ((u.seq0 + u.total - m1 + tt) % kRR) * CW1, smem, ro, CW1, tid & 63, 64);
+        }
+        for (int idx = tid; idx < m2 * nq; idx += 256) {
+            const int tt = fdiv(g.dnq, idx), q = idx - tt * nq, r = prow0 + cntp - m2 + tt;
+            uint8_t v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int b = min(4 * q + e, SK2 - 1);
+                const int s = fdiv(g.dk2, b), i = b - s * k2;
+                v[e] = planes[(i * ROWS2 + r) * SP2 + s];
+            }
+            uint8_t* dst = win2 + ((u.seq0 - T1 + u.total - m2 + tt) % W2) * SK2 + 4 * q;
+            if ((SK2 & 3) == 0) {  // then dst is a dword address
+                *reinterpret_cast<uint32_t*>(dst) = uint32_t(v[0]) | (uint32_t(v[1]) << 8) | (uint32_t(v[2]) << 16) |
+                                                    (uint32_t(v[3]) << 24);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (4 * q + e < SK2) dst[e] = v[e];
+            }
+        }
+    };
+
+    // ---- the windows of the H2 messages in front of the chunk: from the window ring (a message before
+    // the flow's first is a zero window), or decoded again from the call's rows
+    int nfront = 0;
+    if (first) {
+        for (int idx = tid; idx < H2 * nq; idx += 256) {
+            const int r = fdiv(g.dnq, idx), q = idx - r * nq;
+            const int64_t e = u.seq0 - T1 + r - H2;
+            uint32_t w = 0;
+            if (e >= 0) {
+                const uint8_t* src = win2 + (e % W2) * SK2 + 4 * q;
+                if ((SK2 & 3) == 0) {  // then src is a dword address
+                    w = *reinterpret_cast<const uint32_t*>(src);
+                } else {
+                    for (int x = 0; x < 4; ++x)
+                        if (4 * q + x < SK2) w |= uint32_t(src[x]) << (8 * x);
+                }
+            }
+            int s = fdiv(g.dk2, 4 * q), i = 4 * q - s * k2;
+#pragma unroll
+            for (int x = 0; x < 4; ++x) {
+                if (4 * q + x < SK2) planes[(i * ROWS2 + r) * SP2 + s] = static_cast<uint8_t>(w >> (8 * x));
+                if (++i == k2) i = 0, ++s;
+            }
+        }
+    } else {
+        nfront = decode_pass(u.row0 - H2, u.seq0 - H2, H2, u.lead - H2, u.coef, 0);
+        __syncthreads();  // its rows and row records give way to the chunk's own
+    }
+    // ---- the chunk's own messages
+    decode_pass(u.row0, u.seq0, u.cnt, u.lead, u.coef + static_cast<int64_t>(nfront) * kn1, H2);
+    __syncthreads();  // the planes are complete
+    const bool far = u.total > u.cnt;  // the burst's last rows lie behind this chunk
+    if (first) {
+        if (!far) write_rings(u.cnt, H2);
+        __syncthreads();  // the staged codewords give way to the hop-2 codewords
+    }
+    // ---- encode, as burst_encode_chunk: systematic bytes, parity columns, trimmed sizes, flush
+    uint8_t* gcw = a.cw_out + u.row0 * CW2;
+    const int ao = g.off_rows + static_cast<int>(reinterpret_cast<uintptr_t>(gcw) & 3);
+    uint8_t* out = smem + ao;  // the chunk's codewords, packed at CW2
+    for (int idx = tid; idx < u.cnt * nq; idx += 256) {
+        const int p = fdiv(g.dnq, idx), q = idx - p * nq;
+        int s = fdiv(g.dk2, 4 * q), i = 4 * q - s * k2;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * q + e < SK2) out[p * CW2 + s * n2 + i] = planes[(i * ROWS2 + p + H2) * SP2 + s];
+            if (++i == k2) i = 0, ++s;
+        }
+    }
+    // parity column j of four sub-streams: XOR_i G[i][j] * X_{t-(j-i)}[s][i]; rows without a message are zero
+    for (int jj = 0; jj < np2; ++jj) {
+        const int j = k2 + jj;
+        for (int it = tid; it < u.cnt * NS4; it += 256) {
+            const int p = fdiv(g.dns4, it), gq = it - p * NS4;
+            uint32_t acc = 0;
+            for (int i = 0; i < k2; ++i) {
+                const uint32_t* t = tab + (i * np2 + jj) * 8;
+                if (!t[5]) continue;
+                const int r = p + H2 - (j - i);
+                acc ^= gf_mul4x(t, *reinterpret_cast<const uint32_t*>(planes + (i * ROWS2 + r) * SP2 + 4 * gq));
+            }
+            uint8_t* o = out + p * CW2 + 4 * gq * n2 + j;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * gq + e < S2) o[e * n2] = static_cast<uint8_t>(acc >> (8 * e));
+        }
+    }
+    __syncthreads();
+    if (tid < u.cnt) {
+        a.cw_len[u.row0 + tid] = last_nonzero_end(out + tid * CW2, CW2);  // FEC_Encoder.cpp:55-60
+        if (a.fate) a.fate[u.row0 + tid] = a.flags[u.row0 + tid] & 3;
+    }
+    burst_flush(gcw, smem, ao, u.cnt * CW2, tid, 256);
+    if (!first || !far) return;
+    // ---- first chunk of a burst cut in several: the burst's last rows again, for the rings
+    __syncthreads();
+    const int mt = max(m2, 1);
+    decode_pass(u.row0 + u.total - mt, u.seq0 + u.total - mt, mt, u.total - mt, u.tail_coef, 0);
+    __syncthreads();
+    write_rings(mt, 0);
+}
+
+constexpr size_t mw_align16(size_t v) { return (v + 15) & ~size_t(15); }
+
+// LDS carve-up for chunks of tp packets: fills the geometry but the pointers; returns its bytes
+int mw_lds(const Geometry& g1, const Geometry& g2, int tp, MwGeom* a) {
+    a->L = g1.L, a->T1 = g1.T, a->k1 = g1.k, a->n1 = g1.n, a->CW1 = g1.CW;
+    a->CWD1 = (g1.CW + 6) >> 2;
+    a->CWS1 = 4 * a->CWD1;
+    a->HR1 = g1.T + g1.k - 1;
+    const int np2 = g2.n - g2.k;
+    a->k2 = g2.k, a->n2 = g2.n, a->S2 = g2.S, a->CW2 = g2.CW, a->SK2 = g2.S * g2.k;
+    a->NS4 = (g2.S + 3) / 4;
+    a->SP2 = 4 * a->NS4;
+    a->H2 = g2.n - 1;
+    a->W2 = std::max(1, a->H2);
+    a->TP = tp;
+    // a burst is cut only into chunks of at least HR1 + H2 packets; then a pass may hold the H2 messages in
+    // front of a chunk, or the burst's last max(H2, 1) for the rings
+    a->PR = tp >= a->HR1 + a->H2 ? std::max({tp, a->H2, 1}) : tp;
+    a->ROWS1 = a->HR1 + a->PR;
+    a->ROWS2 = a->H2 + tp;
+    size_t off = mw_align16(static_cast<size_t>(std::max(1, g2.k * np2)) * 32);
+    a->off_gf = static_cast<int>(off);
+    off += 768;
+    a->off_rows = static_cast<int>(off);
+    off = mw_align16(off + std::max(static_cast<size_t>(a->ROWS1) * a->CWS1, static_cast<size_t>(tp) * g2.CW + 32));
+    a->off_coef = static_cast<int>(off);
+    off = mw_align16(off + static_cast<size_t>(a->PR) * g1.k * g1.n + 16);
+    a->off_planes = static_cast<int>(off);
+    off = mw_align16(off + static_cast<size_t>(g2.k) * a->ROWS2 * a->SP2);
+    a->off_meta = static_cast<int>(off);
+    off = mw_align16(off + static_cast<size_t>(a->ROWS1) * 4 + static_cast<size_t>(a->PR) * 9);
+    a->dk1 = fast_div(g1.k);
+    a->dk2 = fast_div(g2.k);
+    a->dns4 = fast_div(a->NS4);
+    a->dnq = fast_div((a->SK2 + 3) >> 2);
+    a->dcwd = fast_div(a->CWD1);
+    return static_cast<int>(std::min<size_t>(off, 1u << 30));
+}
+
+// One hop's tuple as fec_streams_create takes it at this payload size (fec_codec_create's bounds, then
+// the stream kernels').
+bool mw_tuple(int L, int T, int B, int N, Geometry* g) {
+    try {
+        *g = Geometry::make(L, T, B, N);
+    } catch (const std::invalid_argument&) {
+        return false;
+    }
+    if (g->L > 1500 || g->B < g->N || g->n > kMaxN - 1) return false;
+    return g->T + g->k <= kRR && g->k <= 16 && g->k * g->n <= 16 * 32;
+}
+
+// The chunk of a burst cut in several: the most packets <= kMwTP whose LDS fits, at least the HR1 + H2
+// a later chunk needs in front of it.  0: not even that fits.
+int mw_fit(const Geometry& g1, const Geometry& g2, MwGeom* a, int* lds) {
+    const int front = std::max(1, g1.T + g1.k - 1 + g2.n - 1);
+    for (int tp = kMwTP; tp >= front; --tp) {
+        *lds = mw_lds(g1, g2, tp, a);
+        if (*lds <= kMwLds) return tp;
+    }
+    return 0;
+}
+
+}  // namespace
+}  // namespace fec
+
+struct fec_mw_relay_streams {
+    std::unique_ptr<StepPool> pool;          // symbolic steps of large calls (FEC_STREAMS_THREADS)
+    fec_codec* c1 = nullptr;                 // hop 1: the GF tables
+    fec_codec* c2 = nullptr;                 // hop 2: the parity tables
+    fec::Geometry g1, g2;
+    int tpmax = 0, nstreams = 0;
+    std::shared_ptr<const fec::DecodeRules> rules;
+    std::vector<std::unique_ptr<fec::StreamPlanner>> planners;
+    std::vector<int64_t> seq;                // hop-1 packets fed so far per flow
+    std::vector<uint32_t> mark;              // duplicate-id check (call stamp per flow)
+    uint32_t stamp = 0;
+    uint8_t* d_ring1 = nullptr;
+    uint8_t* d_win2 = nullptr;
+    // Per-call records (chunks, row flags, coefficient blocks) go through a ring of pinned, mapped
+    // staging buffers that the kernel reads in place (as fec_streams'): a buffer is rewritten only
+    // after the kernel that read it.
+    static constexpr int kStageBufs = 4;
+    void* h_stage[kStageBufs] = {};
+    void* m_stage[kStageBufs] = {};
+    size_t stage_cap[kStageBufs] = {};
+    hipEvent_t staged[kStageBufs] = {};
+    int buf = 0;
+    hipEvent_t done = nullptr;               // the last call's kernel (rings)
+    bool poisoned = false;                   // a failed call left host and device state apart
+    ~fec_mw_relay_streams() {
+        for (hipEvent_t e : staged)
+            if (e) (void)hipEventDestroy(e);
+        if (done) (void)hipEventDestroy(done);
+        for (void* p : {static_cast<void*>(d_ring1), static_cast<void*>(d_win2)})
+            if (p) (void)hipFree(p);
+        for (void* p : h_stage)
+            if (p) (void)hipHostFree(p);
+        if (c1) fec_codec_destroy(c1);
+        if (c2) fec_codec_destroy(c2);
+    }
+};
+
+namespace {
+
+int mw_stage_reserve(fec_mw_relay_streams* h, int b, size_t bytes) {
+    if (bytes <= h->stage_cap[b]) return FEC_OK;
+    const size_t cap = std::max(bytes, 2 * h->stage_cap[b]);
+    if (h->h_stage[b]) FEC_HIP(hipHostFree(h->h_stage[b]));
+    h->h_stage[b] = nullptr;
+    h->m_stage[b] = nullptr;
+    h->stage_cap[b] = 0;
+    FEC_HIP(hipHostMalloc(&h->h_stage[b], cap, hipHostMallocMapped));
+    FEC_HIP(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
+    h->stage_cap[b] = cap;
+    return FEC_OK;
+}
+
+// A launch with more than 64 KB of dynamic LDS needs the kernel's limit raised first.
+int mw_lds_allow(int lds) {
+    static std::mutex mu;
+    static int raised = 0;
+    std::lock_guard<std::mutex> lk(mu);
+    if (lds <= 64 * 1024 || lds <= raised) return FEC_OK;
+    FEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fec::fec_mw_relay_streams_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    raised = lds;
+    return FEC_OK;
+}
+
+int mw_relay_call(fec_mw_relay_streams* h, const int32_t* ids, const int32_t* counts, int M, const uint8_t* erasure,
+                  const uint8_t* d_cw1, int64_t cw1_stride, uint8_t* d_cw2, int32_t* d_cw2_len, uint8_t* d_fate,
+                  hipStream_t s) {
+    if (M < 0 || M > h->nstreams) return FEC_ERR_ARG;
+    if (M == 0) return FEC_OK;
+    if (!ids || !erasure || !d_cw1 || !d_cw2 || !d_cw2_len || cw1_stride < h->g1.CW) return FEC_ERR_ARG;
+    int64_t R = M;
+    int maxc = 1;
+    if (counts) {
+        R = 0;
+        for (int m = 0; m < M; ++m) {
+            if (counts[m] < 1) return FEC_ERR_ARG;
+            R += counts[m];
+            maxc = std::max(maxc, counts[m]);
+        }
+    }
+    if (++h->stamp == 0) {
+        std::fill(h->mark.begin(), h->mark.end(), 0u);
+        h->stamp = 1;
+    }
+    for (int m = 0; m < M; ++m) {
+        const int id = ids[m];
+        if (id < 0 || id >= h->nstreams || h->mark[id] == h->stamp) return FEC_ERR_ARG;
+        h->mark[id] = h->stamp;
+    }
+    // bursts are one chunk each when the call's longest fits the chunk; else chunks of tpmax >= HR1 + H2
+    const int tp = std::min(maxc, h->tpmax);
+    fec::MwArgs a{};
+    const int lds = fec::mw_lds(h->g1, h->g2, tp, &a.g);
+    int64_t nu = 0;
+    for (int m = 0; m < M; ++m) nu += ((counts ? counts[m] : 1) + tp - 1) / tp;
+    if (nu > INT32_MAX) return FEC_ERR_ARG;
+    if (h->poisoned) return FEC_ERR_HIP;
+    // The symbolic decoders advance before the launch: a failure from here on leaves the host planners
+    // ahead of the device rings (or the staging ring in an unknown state), and the group refuses every
+    // later call.
+    struct Poison {
+        fec_mw_relay_streams* h;
+        bool armed = true;
+        ~Poison() { if (armed) h->poisoned = true; }
+    } poison{h};
+    if (int st = mw_lds_allow(lds)) return st;
+    // This call's staging buffer is free once the call that used it last has run; the previous call's
+    // kernel (the rings' last reader and writer) comes before this one's on any stream.
+    const int b = h->buf;
+    FEC_HIP(hipEventSynchronize(h->staged[b]));
+    FEC_HIP(hipStreamWaitEvent(s, h->done, 0));
+    const fec::Geometry& g1 = h->g1;
+    const int kn1 = g1.k * g1.n, H2 = h->g2.n - 1;
+    // flows are independent: contiguous parts of them, one per thread; a flow's recovered rows keep their
+    // coefficient blocks in row order, so the blocks of any run of its rows are one range
+    const int np = (h->pool && R >= 2 * kPoolMinItems) ? h->pool->parts() : 1;
+    std::vector<int64_t> row_at(M + 1, 0), unit_at(M + 1, 0);
+    for (int m = 0; m < M; ++m) {
+        const int cnt = counts ? counts[m] : 1;
+        row_at[m + 1] = row_at[m] + cnt;
+        unit_at[m + 1] = unit_at[m] + (cnt + tp - 1) / tp;
+    }
+    std::vector<uint8_t> flags(static_cast<size_t>(R));
+    std::vector<fec::MwUnit> units(static_cast<size_t>(nu));
+    std::vector<std::vector<uint8_t>> coefs(np);
+    std::atomic<bool> failed{false};
+    auto part = [&](int p) {
+        if (p < 0 || p >= np) return;
+        try {
+            const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
+            const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
+            for (int m = m0; m < m1; ++m) {
+                const int id = ids[m], cnt = counts ? counts[m] : 1;
+                const int64_t seq = h->seq[id], base = static_cast<int64_t>(coefs[p].size());
+                const uint8_t* fr = flags.data() + row_at[m];
+                plan_burst_rows(*h->planners[id], g1.T, kn1, seq, erasure + row_at[m], cnt, flags.data() + row_at[m],
+                                coefs[p]);
+                // a chunk's blocks start with those of its first decoded row: H2 rows in front of a later chunk
+                int pos = 0;
+                int64_t rec = 0;
+                auto blocks_before = [&](int row) {
+                    for (; pos < row; ++pos) rec += (fr[pos] & 3) == fec::kRecovered;
+                    return base + rec * kn1;
+                };
+                fec::MwUnit* u = units.data() + unit_at[m];
+                for (int lead = 0; lead < cnt; lead += tp, ++u) {
+                    u->row0 = row_at[m] + lead;
+                    u->seq0 = seq + lead;
+                    u->coef = blocks_before(std::max(lead - H2, 0));
+                    u->tail_coef = 0;
+                    u->id = id;
+                    u->cnt = std::min(tp, cnt - lead);
+                    u->lead = lead;
+                    u->total = cnt;
+                }
+                if (cnt > tp) {  // the first chunk decodes the burst's last max(min(messages, H2), 1) rows again
+                    const int nmsg = cnt - static_cast<int>(std::min<int64_t>(std::max<int64_t>(g1.T - seq, 0), cnt));
+                    units[unit_at[m]].tail_coef = blocks_before(cnt - std::max(std::min(nmsg, H2), 1));
+                }
+            }
+        } catch (...) {
+            failed.store(true);
+        }
+    };
+    if (np > 1)
+        h->pool->run(part);
+    else
+        part(0);
+    if (failed.load()) return FEC_ERR_ARG;
+    // staging: units | row flags | coefficient blocks
+    const size_t off_flags = fec::mw_align16(static_cast<size_t>(nu) * sizeof(fec::MwUnit));
+    const size_t off_coef = fec::mw_align16(off_flags + static_cast<size_t>(R));
+    size_t ncoef = 0;
+    for (const auto& c : coefs) ncoef += c.size();
+    if (int st = mw_stage_reserve(h, b, off_coef + ncoef + 16)) return st;
+    uint8_t* hs = static_cast<uint8_t*>(h->h_stage[b]);
+    size_t cbase = 0;
+    for (int p = 0; p < np; ++p) {  // a part's blocks follow those of the parts before it
+        const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
+        const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
+        if (cbase)
+            for (int64_t ui = unit_at[m0]; ui < unit_at[m1]; ++ui) {
+                units[ui].coef += static_cast<int64_t>(cbase);
+                units[ui].tail_coef += static_cast<int64_t>(cbase);
+            }
+        if (!coefs[p].empty()) std::memcpy(hs + off_coef + cbase, coefs[p].data(), coefs[p].size());
+        cbase += coefs[p].size();
+    }
+    std::memcpy(hs, units.data(), units.size() * sizeof(fec::MwUnit));
+    std::memcpy(hs + off_flags, flags.data(), flags.size());
+    const uint8_t* rec = static_cast<const uint8_t*>(h->m_stage[b]);
+    fec::CodecView v1, v2;
+    if (int st = fec::codec_view(h->c1, &v1)) return st;
+    if (int st = fec::codec_view(h->c2, &v2)) return st;
+    a.cw_in = d_cw1;
+    a.stride = cw1_stride;
+    a.flags = rec + off_flags;
+    a.coefs = rec + off_coef;
+    a.cw_out = d_cw2;
+    a.cw_len = d_cw2_len;
+    a.fate = d_fate;
+    a.units = reinterpret_cast<const fec::MwUnit*>(rec);
+    a.ring1 = h->d_ring1;
+    a.win2 = h->d_win2;
+    a.g.gf = v1.gf;
+    a.g.ptab = v2.ptab;
+    hipLaunchKernelGGL(fec::fec_mw_relay_streams_kernel, dim3(static_cast<unsigned>(nu)), dim3(256),
+                       static_cast<size_t>(lds), s, a);
+    FEC_HIP(hipGetLastError());
+    FEC_HIP(hipEventRecord(h->done, s));
+    FEC_HIP(hipEventRecord(h->staged[b], s));
+    h->buf = (b + 1) % fec_mw_relay_streams::kStageBufs;
+    for (int m = 0; m < M; ++m) h->seq[ids[m]] += counts ? counts[m] : 1;
+    poison.armed = false;
+    return FEC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fec_mw_relay_streams_fit(int max_payload, int T1, int B1, int N1, int T2, int B2, int N2, int* chunk_packets,
+                             int* lds_bytes) {
+    fec::Geometry g1, g2;
+    if (!fec::mw_tuple(max_payload, T1, B1, N1, &g1) || !fec::mw_tuple(max_payload, T2, B2, N2, &g2)) return FEC_ERR_ARG;
+    fec::MwGeom a{};
+    int lds = 0;
+    const int tp = fec::mw_fit(g1, g2, &a, &lds);
+    if (!tp) return FEC_ERR_ARG;
+    if (chunk_packets) *chunk_packets = tp;
+    if (lds_bytes) *lds_bytes = lds;
+    return FEC_OK;
+}
+
+int fec_mw_relay_streams_create(int max_payload, int T1, int B1, int N1, int T2, int B2, int N2, int nstreams,
+                                fec_mw_relay_streams** out) {
+    if (!out) return FEC_ERR_ARG;
+    *out = nullptr;
+    if (nstreams <= 0) return FEC_ERR_ARG;
+    try {
+        // everything that can refuse the arguments comes before the first allocation
+        fec::Geometry g1, g2;
+        if (!fec::mw_tuple(max_payload, T1, B1, N1, &g1) || !fec::mw_tuple(max_payload, T2, B2, N2, &g2))
+            return FEC_ERR_ARG;
+        fec::MwGeom geo{};
+        int lds = 0;
+        const int tpmax = fec::mw_fit(g1, g2, &geo, &lds);
+        if (!tpmax) return FEC_ERR_ARG;
+        std::unique_ptr<fec_mw_relay_streams> h(new fec_mw_relay_streams());
+        if (int st = fec_codec_create(max_payload, T1, B1, N1, &h->c1)) return st;
+        if (int st = fec_codec_create(max_payload, T2, B2, N2, &h->c2)) return st;
+        h->g1 = g1, h->g2 = g2, h->tpmax = tpmax, h->nstreams = nstreams;
+        h->rules = fec::shared_decode_rules(T1, B1, N1);
+        h->planners.resize(nstreams);
+        for (auto& p : h->planners) p.reset(new fec::StreamPlanner(g1, h->rules.get()));
+        {
+            const int hw = allowed_cpus();  // not hardware_concurrency: the process's cpuset may be smaller
+            int nth = std::max(1, std::min(hw > 1 ? hw - 1 : 1, 8));
+            if (const char* e = std::getenv("FEC_STREAMS_THREADS")) nth = std::max(1, std::atoi(e));
+            if (nth > 1 && nstreams >= 2 * kPoolMinItems) h->pool.reset(new StepPool(nth));
+        }
+        h->seq.assign(nstreams, 0);
+        h->mark.assign(nstreams, 0);
+        const size_t rb = static_cast<size_t>(nstreams) * fec::kRR * g1.CW;
+        const size_t wb = static_cast<size_t>(nstreams) * geo.W2 * geo.SK2;
+        FEC_HIP(hipMalloc(&h->d_ring1, rb));
+        FEC_HIP(hipMemset(h->d_ring1, 0, rb));
+        FEC_HIP(hipMalloc(&h->d_win2, wb));
+        FEC_HIP(hipMemset(h->d_win2, 0, wb));
+        const size_t stage = static_cast<size_t>(nstreams) * (sizeof(fec::MwUnit) + 1 + g1.k * g1.n + 16) + 64;
+        for (int b = 0; b < fec_mw_relay_streams::kStageBufs; ++b) {
+            if (int st = mw_stage_reserve(h.get(), b, stage)) return st;
+            FEC_HIP(hipEventCreateWithFlags(&h->staged[b], hipEventDisableTiming));
+            FEC_HIP(hipEventRecord(h->staged[b], nullptr));
+        }
+        FEC_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
+        FEC_HIP(hipEventRecord(h->done, nullptr));
+        *out = h.release();
+        return FEC_OK;
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    } catch (...) {
+        return FEC_ERR_ARG;
+    }
+}
+
+int fec_mw_relay_streams_destroy(fec_mw_relay_streams* h) {
+    delete h;
+    return FEC_OK;
+}
+
+int fec_mw_relay_streams_geometry(const fec_mw_relay_streams* h, int* cw1_bytes, int* cw2_bytes, int* delay) {
+    if (!h) return FEC_ERR_ARG;
+    if (cw1_bytes) *cw1_bytes = h->g1.CW;
+    if (cw2_bytes) *cw2_bytes = h->g2.CW;
+    if (delay) *delay = h->g1.T;
+    return FEC_OK;
+}
+
+int fec_mw_relay_streams_relay(fec_mw_relay_streams* h, const int32_t* ids, const int32_t* counts, int M,
+                               const uint8_t* erasure, const uint8_t* d_cw1, int64_t cw1_stride, uint8_t* d_cw2,
+                               int32_t* d_cw2_len, uint8_t* d_fate, void* stream) {
+    if (!h) return FEC_ERR_ARG;
+    try {
+        return mw_relay_call(h, ids, counts, M, erasure, d_cw1, cw1_stride, d_cw2, d_cw2_len, d_fate,
+                             static_cast<hipStream_t>(stream));
+    } catch (const std::bad_alloc&) {
+        return FEC_ERR_NOMEM;
+    } catch (...) {
+        return FEC_ERR_ARG;
+    }
+}
+
+int fec_mw_relay_streams_state(const fec_mw_relay_streams* h, int id, int64_t* received, int64_t* forwarded) {
+    if (!h || id < 0 || id >= h->nstreams) return FEC_ERR_ARG;
+    if (received) *received = h->seq[id];
+    if (forwarded) *forwarded = std::max<int64_t>(h->seq[id] - h->g1.T, 0);
+    return FEC_OK;
+}
+
+}  // extern "C"

@@ -270,6 +270,82 @@ def relay_streams_plan_host(k: int, n: int, erasure, counts):
     return mask, flag
 
 
+class MessageWiseRelayGroup:
+    """``nstreams`` independent message-wise (type-1) relays at fixed rate, all of one (max_payload,
+    code1 = (T1, B1, N1), code2 = (T2, B2, N2)) (fec_mw_relay_streams_*): per flow an FEC_Decoder of
+    code1 feeding an FEC_Encoder of code2, its state on the device between calls.  Each call hands
+    over the next packet, or the next ``counts[m]`` packets, of every listed flow and decodes and
+    re-encodes them in one launch; per flow the rows of all calls together are
+    StreamGroup(code1).decode_burst over the flow's hop-1 sequence, the first T1 rows dropped, then
+    StreamGroup(code2).encode_burst.  The destination is StreamGroup(max_payload, *code2).decode_burst.
+    This is not the reference's adaptive message-wise session (relay headers, acknowledgements)."""
+
+    def __init__(self, max_payload: int, code1, code2, nstreams: int):
+        (T1, B1, N1), (T2, B2, N2) = code1, code2
+        h = ctypes.c_void_p()
+        check(lib().fec_mw_relay_streams_create(max_payload, T1, B1, N1, T2, B2, N2, nstreams, ctypes.byref(h)),
+              "fec_mw_relay_streams_create")
+        self._h = h
+        v = [ctypes.c_int() for _ in range(3)]
+        check(lib().fec_mw_relay_streams_geometry(h, *[ctypes.byref(x) for x in v]), "fec_mw_relay_streams_geometry")
+        self.cw1_bytes, self.cw2_bytes, self.delay = (x.value for x in v)
+        self.L, self.nstreams = max_payload, nstreams
+        self.code1, self.code2 = (T1, B1, N1), (T2, B2, N2)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().fec_mw_relay_streams_destroy(self._h)
+            except Exception:
+                pass
+            self._h = None
+
+    def relay(self, ids, counts, erasure, codewords, out=None, out_len=None, fate=None):
+        """The next counts[m] hop-1 seqs of flow ids[m] (counts None: one of each): codewords [R, >=
+        cw1_bytes] uint8 on the GPU, untrimmed (flow ids[m]'s from row sum(counts[:m]) on; any row
+        stride, any alignment; rows of erased packets are never read), erasure R host flags ->
+        (hop-2 codewords [R, cw2_bytes] uint8, trimmed sizes [R] int32, fates [R] uint8: 0 none, 1
+        copied, 2 recovered, 3 lost) on the GPU.  A row of hop-1 seq < delay is zero with size 0."""
+        import torch
+        ids, counts, er, R = RelayStreamGroup._rows(ids, counts, erasure)
+        assert codewords.dtype == torch.uint8 and codewords.is_cuda and codewords.dim() == 2
+        assert codewords.shape[0] == R and (R == 0 or codewords.stride(1) == 1)
+        dev = codewords.device
+        if out is None:
+            out = torch.empty((R, self.cw2_bytes), dtype=torch.uint8, device=dev)
+        assert tuple(out.shape) == (R, self.cw2_bytes) and out.is_contiguous() and out.dtype == torch.uint8
+        if out_len is None:
+            out_len = torch.empty(R, dtype=torch.int32, device=dev)
+        assert out_len.numel() >= R and out_len.dtype == torch.int32 and out_len.is_contiguous()
+        if fate is None:
+            fate = torch.empty(R, dtype=torch.uint8, device=dev)
+        assert fate.numel() >= R and fate.dtype == torch.uint8 and fate.is_contiguous()
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        h = RelayStreamGroup._host
+        # the row stride goes to the library as it is: a stride below cw1_bytes is the library's to refuse
+        check(lib().fec_mw_relay_streams_relay(self._h, h(ids), h(counts), ids.size, h(er), _ptr(codewords),
+                                               codewords.stride(0) if R else self.cw1_bytes, _ptr(out),
+                                               _ptr(out_len), _ptr(fate), stream), "fec_mw_relay_streams_relay")
+        return out, out_len, fate
+
+    def state(self, stream_id: int):
+        """(hop-1 packets received, messages forwarded) of one flow."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        check(lib().fec_mw_relay_streams_state(self._h, stream_id, ctypes.byref(a), ctypes.byref(b)),
+              "fec_mw_relay_streams_state")
+        return a.value, b.value
+
+
+def mw_relay_streams_fit(max_payload: int, code1, code2):
+    """Host only: (packets per chunk of a burst cut in several, that chunk's LDS bytes) of a
+    message-wise relay group of code1 = (T1, B1, N1) -> code2 = (T2, B2, N2); FecError for a pair the
+    group refuses (a tuple StreamGroup refuses, or a smallest chunk that does not fit)."""
+    tp, lds = ctypes.c_int(), ctypes.c_int()
+    check(lib().fec_mw_relay_streams_fit(max_payload, *code1, *code2, ctypes.byref(tp), ctypes.byref(lds)),
+          "fec_mw_relay_streams_fit")
+    return tp.value, lds.value
+
+
 class StateDependentRelay:
     """Fixed-rate SD-SWDF chain (RELAYING_TYPE 3): source (T1, N1, N1) -> relay
     (symbol_wise_encode_state_dependent, Decoder_Symbol_Wise.cpp:178-432) -> destination

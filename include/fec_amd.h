@@ -509,6 +509,56 @@ int fec_relay_streams_fit(int relay, int max_payload, int T1, int N1, int T2, in
 int fec_relay_streams_plan_host(int k, int n, const uint8_t *erasure, const int32_t *counts, int ncounts,
                                 uint32_t *mask, uint8_t *flag);
 
+/* ---- message-wise relay stream groups: hop-1 decode and hop-2 encode in one launch -------------
+ * nstreams independent type-1 (message-wise decode-and-forward) relays at fixed rate, all of one
+ * (max_payload, T1,B1,N1, T2,B2,N2), each flow's state on the device between calls: per flow an
+ * FEC_Decoder of the hop-1 code (FEC_Decoder.cpp:38-75; its ring of received codewords :55-63,
+ * Decoder::decodeStream, Decoder.cpp:72-175) feeding an FEC_Encoder of the hop-2 code
+ * (FEC_Encoder.cpp:38-62; the window of Encoder.cpp:73-95, the trimmed size FEC_Encoder.cpp:55-60),
+ * one packet or a burst per call.  Both tuples must be ones fec_streams_create takes at
+ * max_payload.  This is the fixed-rate relay of the per-packet contract; the reference's adaptive
+ * message-wise session (Variable_Rate_FEC_Decoder's stored messages, the 12-byte relay header,
+ * T2_ack) is not built here.  The destination is an ordinary (T2,B2,N2) decoder:
+ * fec_streams_decode_burst of a fec_streams group serves it, and there is no destination entry.
+ *
+ * Rows as in fec_relay_streams_relay: ids M distinct flow ids (host); counts M burst sizes >= 1
+ * (host; NULL: one packet of each); R = the sum of the counts; erasure R host flags; d_cw1 R rows of
+ * cw1_stride >= cw1_bytes = S1*n1 bytes, the flow's next hop-1 codewords untrimmed (rows of erased
+ * packets are never read); d_cw2 R rows of cw2_bytes = S2*n2; d_cw2_len R trimmed wire sizes (as
+ * fec_streams_encode_burst's); d_fate R bytes (may be NULL): 0 none, 1 copied, 2 recovered, 3 lost
+ * (fec_plan_host's encoding).  For hop-1 seq t of a flow: t < T1 gives a zero row, size 0, fate 0,
+ * and the hop-2 encoder does not advance; t >= T1 gives the hop-2 codeword number t - T1 of the
+ * message the hop-1 decoder outputs at seq t, its length clipped to [0, max_payload]; a message the
+ * relay loses is forwarded as the empty message, so relay seq and source seq stay equal.
+ * Per flow the rows of all calls together equal fec_streams_decode_burst over the flow's hop-1
+ * sequence, the first T1 rows dropped, then fec_streams_encode_burst over the rest -- byte for byte
+ * with the zero pad, sizes and fates too, whatever the cutting into calls and whichever flows share
+ * a call.  No pointer or row needs any alignment.  Calls on different HIP streams are ordered by
+ * the group.
+ * One workgroup per chunk of at most 32 packets decodes its messages straight into the encoder's
+ * position planes in LDS and encodes them: no payload row is written or read.  A chunk behind a
+ * burst's first decodes the n2-1 messages in front of it again, so a burst cut in several has
+ * chunks of at least T1+k1-1 + n2-1 packets (fec_mw_relay_streams_fit).
+ * FEC_ERR_ARG (group unchanged): a repeated or out-of-range id, a count < 1, a null pointer,
+ * cw1_stride < cw1_bytes; at create a tuple fec_streams_create refuses, or a pair whose smallest
+ * chunk T1+k1-1 + n2-1 exceeds 32 packets or a CU's 160 KB of LDS ((24,12,12) -> (24,12,12)).  Any
+ * later failure poisons the group (every further call returns FEC_ERR_HIP). */
+typedef struct fec_mw_relay_streams fec_mw_relay_streams;
+int fec_mw_relay_streams_create(int max_payload, int T1, int B1, int N1, int T2, int B2, int N2, int nstreams,
+                                fec_mw_relay_streams **out);
+int fec_mw_relay_streams_destroy(fec_mw_relay_streams *group);
+/* cw1_bytes = S1*n1, cw2_bytes = S2*n2, delay = T1 (any pointer may be NULL) */
+int fec_mw_relay_streams_geometry(const fec_mw_relay_streams *group, int *cw1_bytes, int *cw2_bytes, int *delay);
+int fec_mw_relay_streams_relay(fec_mw_relay_streams *group, const int32_t *ids, const int32_t *counts, int M,
+                               const uint8_t *erasure, const uint8_t *d_cw1, int64_t cw1_stride, uint8_t *d_cw2,
+                               int32_t *d_cw2_len, uint8_t *d_fate, void *hip_stream);
+/* hop-1 packets flow id has been fed so far, and messages forwarded (= max(received - T1, 0)) */
+int fec_mw_relay_streams_state(const fec_mw_relay_streams *group, int id, int64_t *received, int64_t *forwarded);
+/* Host only, no device call: the packets per chunk of a burst cut in several and that chunk's LDS
+ * bytes, through the routine create uses.  FEC_ERR_ARG where create would refuse the pair. */
+int fec_mw_relay_streams_fit(int max_payload, int T1, int B1, int N1, int T2, int B2, int N2, int *chunk_packets,
+                             int *lds_bytes);
+
 /* ---- relay: state-dependent symbol-wise decode-and-forward (SD-SWDF, RELAYING_TYPE 3) --------
  * Decoder_Symbol_Wise::symbol_wise_encode_state_dependent (src/Decoder_Symbol_Wise.cpp:178-432) at
  * the relay and symbol_wise_decode_state_dependent + extract_data (:487-546, :653-661) at the

@@ -1,0 +1,391 @@
+"""Message-wise relay stream groups (fec_mw_relay_streams_*) on the GPU: per flow the rows of all relay
+calls together equal the two-call composition they fuse -- the hop-1 decoder's outputs (the first T1
+rows dropped) through the hop-2 encoder with lengths clipped to [0, L] -- whatever the cutting into
+one-packet calls and bursts and whichever flows share a call.  The reference per flow is
+Codec(code1).encode / .decode, then Codec(code2).encode, with fates from plan_host: all checked
+against the oracle by the existing suites.  Needs an MI355X: -m gpu."""
+import numpy as np
+import pytest
+
+from conftest import load_pattern
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+import fec_erasure_code_unit_test_relay_amd as fec  # noqa: E402
+from fec_erasure_code_unit_test_relay_amd.relay import MessageWiseRelayGroup, mw_relay_streams_fit  # noqa: E402
+
+SEED = 0x5EED
+P = 450
+NS = 5
+PAIRS = [((10, 3, 3), (10, 3, 3)), ((10, 5, 2), (6, 2, 2)), ((3, 2, 2), (10, 1, 1)), ((4, 4, 4), (10, 3, 3)),
+         ((10, 1, 1), (4, 4, 4))]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def device():
+    assert torch.cuda.is_available(), "no HIP device"
+    torch.cuda.set_device(0)
+    yield
+
+
+def synthetic_pattern(T, B, N, shift):
+    """P + T flags: runs of B erasures starting at 20, 60, 100, ... while the start is below P - 60,
+    plus one run of T + N + 2 erasures at P / 2, all moved `shift` packets later."""
+    pat = np.zeros(P + T + shift, dtype=np.uint8)
+    start = 20
+    while start < P - 60:
+        pat[shift + start:shift + start + B] = 1
+        start += 40
+    pat[shift + P // 2:shift + P // 2 + T + N + 2] = 1
+    return pat[:P + T]
+
+
+def geometry(code):
+    T, B, N = code
+    k = T - N + 1
+    return k, k + B
+
+
+_codecs = {}
+
+
+def codec(L, code):
+    if (L, code) not in _codecs:
+        _codecs[(L, code)] = fec.Codec(L, *code)
+    return _codecs[(L, code)]
+
+
+def reference(L, code1, code2, pay, lens, pat):
+    """One flow's relay rows from seq 0: (hop-2 codewords, sizes, fates) for its pat.size hop-1 packets."""
+    T1 = code1[0]
+    c1, c2 = codec(L, code1), codec(L, code2)
+    cw1, _ = c1.encode(pay, lens)
+    out, ol = c1.decode(cw1, torch.from_numpy(pat).cuda())
+    cw2, wl2 = c2.encode(out.contiguous(), ol.clamp(0, L).to(torch.int32))
+    fates = torch.from_numpy(fec.plan_host(L, *code1, pat)).cuda()
+    n = pat.size
+    r_cw = torch.zeros((n, cw2.shape[1]), dtype=torch.uint8, device="cuda")
+    r_wl = torch.zeros(n, dtype=torch.int32, device="cuda")
+    r_ft = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    r_cw[T1:], r_wl[T1:], r_ft[T1:] = cw2, wl2, fates
+    torch.cuda.synchronize()
+    return cw1.clone(), r_cw, r_wl, r_ft
+
+
+class Flows:
+    """ns flows of one code pair: payloads, lengths, hop-1 patterns, hop-1 codewords and the reference."""
+
+    def __init__(self, L, code1, code2, ns=NS, seed=41):
+        T1, B1, N1 = code1
+        rng = np.random.default_rng(seed)
+        self.L, self.code1, self.code2, self.ns, self.total = L, code1, code2, ns, P + T1
+        base = load_pattern("bin_erasure").astype(np.uint8)
+        self.pats, self.pay, self.len, self.cw1, self.ref = [], [], [], [], []
+        for s in range(ns):
+            if code1 == (10, 3, 3) and s < 4:
+                self.pats.append(base[7919 * s:7919 * s + P + T1].copy())
+            else:
+                self.pats.append(synthetic_pattern(T1, B1, N1, 7 * s))
+            self.pay.append(fec.fill_payload(0, P + T1, L, SEED + s))
+            ln = rng.integers(0, L + 1, P + T1).astype(np.int32)
+            ln[rng.integers(0, P + T1, 8)] = 0
+            ln[rng.integers(0, P + T1, 8)] = L
+            self.len.append(torch.from_numpy(ln).cuda())
+            cw1, r_cw, r_wl, r_ft = reference(L, code1, code2, self.pay[s], self.len[s], self.pats[s])
+            self.cw1.append(cw1)
+            self.ref.append((r_cw, r_wl, r_ft))
+        # recovered and lost messages are both exercised
+        fates = torch.cat([r[2] for r in self.ref])
+        assert bool((fates == 2).any()) and bool((fates == 3).any())
+        assert all(bool((r[2][:T1] == 0).all()) for r in self.ref)
+
+
+_flows = {}
+
+
+def flows(L, code1, code2):
+    """The reference of a (size, pair), computed once per module and left unchanged."""
+    key = (L, code1, code2)
+    if key not in _flows:
+        _flows[key] = Flows(L, code1, code2)
+    return _flows[key]
+
+
+def cut_counts(code1, code2):
+    (k1, _), (_, n2) = geometry(code1), geometry(code2)
+    HR1, H2 = code1[0] + k1 - 1, n2 - 1
+    c = {1, 2, H2 - 1, H2, HR1, HR1 + H2 - 1, HR1 + H2, HR1 + H2 + 1, 63, 64, 65, 150}
+    return sorted(v for v in c if v >= 1)
+
+
+def received(cw1, er):
+    """Hop-1 rows as the relay gets them: rows of missing packets are never read."""
+    rx = cw1.clone()
+    rx[torch.from_numpy(er.astype(bool)).to(rx.device)] = 0xA5
+    return rx
+
+
+def drive(fl, grp, rng, choices, upto=None, sent=None, got=None):
+    """Feed every flow its packets (up to `upto`) through grp.relay, each call a random subset of the
+    live flows, half of the calls one-packet calls (counts=None), the others with counts from `choices`."""
+    ns, total = fl.ns, fl.total if upto is None else upto
+    if sent is None:
+        sent = np.zeros(ns, dtype=np.int64)
+        got = (torch.zeros((ns, fl.total, grp.cw2_bytes), dtype=torch.uint8, device="cuda"),
+               torch.zeros((ns, fl.total), dtype=torch.int32, device="cuda"),
+               torch.full((ns, fl.total), 9, dtype=torch.uint8, device="cuda"))
+    while (sent < total).any():
+        live = np.flatnonzero(sent < total)
+        ids = rng.permutation(live)[:max(1, int(rng.integers(1, live.size + 1)))].astype(np.int32)
+        single = rng.random() < 0.5
+        counts = np.array([1 if single else min(int(rng.choice(choices)), total - sent[s]) for s in ids],
+                          dtype=np.int32)
+        er = np.concatenate([fl.pats[s][sent[s]:sent[s] + c] for s, c in zip(ids, counts)])
+        rx = received(torch.cat([fl.cw1[s][sent[s]:sent[s] + c] for s, c in zip(ids, counts)]), er)
+        c_cw, c_wl, c_ft = grp.relay(ids, None if single else counts, er, rx)
+        row = 0
+        for s, c in zip(ids, counts):
+            a = sent[s]
+            got[0][s, a:a + c], got[1][s, a:a + c], got[2][s, a:a + c] = (c_cw[row:row + c], c_wl[row:row + c],
+                                                                          c_ft[row:row + c])
+            row += c
+        sent[ids] += counts
+    torch.cuda.synchronize()
+    return sent, got
+
+
+def assert_equal(fl, grp, got, upto=None):
+    T1 = fl.code1[0]
+    n = fl.total if upto is None else upto
+    for s in range(fl.ns):
+        r_cw, r_wl, r_ft = fl.ref[s]
+        assert torch.equal(got[2][s, :n], r_ft[:n]), s
+        assert torch.equal(got[1][s, :n], r_wl[:n]), s
+        assert torch.equal(got[0][s, :n], r_cw[:n]), s
+        assert grp.state(s) == (n, max(n - T1, 0)), s
+
+
+@pytest.mark.parametrize("L,code1,code2", [(300, *p) for p in PAIRS] + [(37, *PAIRS[0])])
+def test_relay_equals_decode_then_encode_under_random_cutting(L, code1, code2):
+    """5 flows of 450 (+T1) packets, random payload sizes (0 and L among them), each call a random subset
+    of the flows, one-packet calls and bursts around n2-1, T1+k1-1, their sum (the least chunk of a burst
+    cut in several) and the ring's 64 rows: every row, size and fate equals the composition's."""
+    fl = flows(L, code1, code2)
+    rng = np.random.default_rng(43)
+    grp = MessageWiseRelayGroup(L, code1, code2, fl.ns)
+    assert (grp.cw1_bytes, grp.delay) == (fl.cw1[0].shape[1], code1[0])
+    _, got = drive(fl, grp, rng, cut_counts(code1, code2))
+    assert_equal(fl, grp, got)
+
+
+def test_messages_in_front_of_a_later_chunk_are_decoded_again():
+    """One burst of 150: a run of B1 erasures whose recovered messages lie among the n2-1 rows in front of
+    the second chunk, and a run of T1+N1+2 whose lost messages lie in front of the third."""
+    L, code1, code2 = 300, (10, 3, 3), (10, 3, 3)
+    (T1, B1, N1), H2 = code1, geometry(code2)[1] - 1
+    tp, _ = mw_relay_streams_fit(L, code1, code2)
+    n = 150
+    assert 2 * tp + 1 < n
+    pat = np.zeros(n, dtype=np.uint8)
+    pat[tp - T1 - 5:tp - T1 - 5 + B1] = 1              # messages output at rows tp-5 .. tp-3
+    pat[2 * tp - T1 - H2 - 4:2 * tp - H2 + N1 - 2] = 1  # T1+N1+2 packets from message 2tp-T1-H2-4 on
+    assert int(pat[2 * tp - T1 - H2 - 4:].sum()) == T1 + N1 + 2
+    fates = fec.plan_burst_host(L, T1, B1, N1, pat, np.array([n], dtype=np.int32))  # fate of message x
+    assert (fates[tp - H2 - T1:tp - T1] == 2).any()          # rows tp-H2 .. tp-1: recovered among them
+    assert (fates[2 * tp - H2 - T1:2 * tp - T1] == 3).any()  # rows 2tp-H2 .. 2tp-1: lost among them
+    pay = fec.fill_payload(0, n, L, SEED + 17)
+    lens = torch.from_numpy(np.random.default_rng(47).integers(0, L + 1, n).astype(np.int32)).cuda()
+    cw1, r_cw, r_wl, r_ft = reference(L, code1, code2, pay, lens, pat)
+    grp = MessageWiseRelayGroup(L, code1, code2, 1)
+    cw, wl, ft = grp.relay(np.array([0], dtype=np.int32), np.array([n], dtype=np.int32), pat, received(cw1, pat))
+    torch.cuda.synchronize()
+    assert torch.equal(ft, r_ft) and torch.equal(wl, r_wl) and torch.equal(cw, r_cw)
+
+
+def test_few_flows_in_bursts_far_longer_than_the_rings():
+    """2 flows x one burst of 2 000 packets, then a one-packet call that continues from the rings the
+    burst's first chunks wrote."""
+    L, code1, code2 = 300, (10, 3, 3), (10, 3, 3)
+    n = 2001
+    base = load_pattern("bin_erasure").astype(np.uint8)
+    pats = [base[7919 * s:7919 * s + n].copy() for s in range(2)]
+    for s, pat in enumerate(pats):  # a run the code recovers and a run it cannot, deep inside the burst
+        pat[700 + 40 * s:700 + 40 * s + code1[1]] = 1
+        pat[1300 + 40 * s:1300 + 40 * s + code1[0] + code1[2] + 2] = 1
+    rng = np.random.default_rng(53)
+    refs, cw1s = [], []
+    for s in range(2):
+        lens = torch.from_numpy(rng.integers(0, L + 1, n).astype(np.int32)).cuda()
+        cw1, *ref = reference(L, code1, code2, fec.fill_payload(0, n, L, SEED + 30 + s), lens, pats[s])
+        cw1s.append(cw1)
+        refs.append(ref)
+        assert bool((ref[2] == 2).any()) and bool((ref[2] == 3).any())
+    grp = MessageWiseRelayGroup(L, code1, code2, 2)
+    ids = np.array([1, 0], dtype=np.int32)
+    er = np.concatenate([pats[s][:n - 1] for s in ids])
+    a = grp.relay(ids, np.full(2, n - 1, dtype=np.int32), er, received(torch.cat([cw1s[s][:n - 1] for s in ids]), er))
+    er1 = np.array([pats[s][n - 1] for s in ids], dtype=np.uint8)
+    b = grp.relay(ids, None, er1, received(torch.stack([cw1s[s][n - 1] for s in ids]), er1))
+    torch.cuda.synchronize()
+    for j, s in enumerate(ids):
+        rows = slice(j * (n - 1), (j + 1) * (n - 1))
+        for x, y, r in zip(a, b, refs[s]):
+            assert torch.equal(x[rows], r[:n - 1]), s
+            assert torch.equal(y[j], r[n - 1]), s
+        assert grp.state(int(s)) == (n, n - code1[0])
+
+
+def test_mtu_size_payloads():
+    """(10,3,3) -> (10,3,3) at L = 1500: the chunk takes nearly all of a CU's 160 KB of LDS (the kernel's
+    raised limit) and holds fewer than 32 packets; 2 flows x one burst of 130 (several chunks), then a
+    one-packet call."""
+    L, code1, code2 = 1500, (10, 3, 3), (10, 3, 3)
+    tp, lds = mw_relay_streams_fit(L, code1, code2)
+    assert tp < 32 and 64 * 1024 < lds <= 160 * 1024
+    n = 131
+    assert n - 1 > 3 * tp
+    rng = np.random.default_rng(67)
+    pats, refs, cw1s = [], [], []
+    for s in range(2):
+        pat = np.zeros(n, dtype=np.uint8)
+        pat[tp - 14 + s:tp - 14 + s + code1[1]] = 1                          # recovered, output around row tp
+        pat[2 * tp - 20 + s:2 * tp - 20 + s + code1[0] + code1[2] + 2] = 1   # lost, output around row 2 tp
+        lens = rng.integers(0, L + 1, n).astype(np.int32)
+        lens[[3, 40]] = [0, L]
+        cw1, *ref = reference(L, code1, code2, fec.fill_payload(0, n, L, SEED + 50 + s),
+                              torch.from_numpy(lens).cuda(), pat)
+        assert bool((ref[2] == 2).any()) and bool((ref[2] == 3).any())
+        pats.append(pat)
+        cw1s.append(cw1)
+        refs.append(ref)
+    grp = MessageWiseRelayGroup(L, code1, code2, 2)
+    ids = np.array([0, 1], dtype=np.int32)
+    er = np.concatenate([p[:n - 1] for p in pats])
+    a = grp.relay(ids, np.full(2, n - 1, dtype=np.int32), er, received(torch.cat([c[:n - 1] for c in cw1s]), er))
+    er1 = np.array([p[n - 1] for p in pats], dtype=np.uint8)
+    b = grp.relay(ids, None, er1, received(torch.stack([c[n - 1] for c in cw1s]), er1))
+    torch.cuda.synchronize()
+    for s in range(2):
+        rows = slice(s * (n - 1), (s + 1) * (n - 1))
+        for x, y, r in zip(a, b, refs[s]):
+            assert torch.equal(x[rows], r[:n - 1]), s
+            assert torch.equal(y[s], r[n - 1]), s
+
+
+def carve(nbytes, off, fill):
+    """A contiguous `nbytes` view `off` bytes past a 256-byte aligned place in a fresh allocation, guard
+    bytes of `fill` on both sides, and a checker that they still hold it."""
+    flat = torch.full((256 + off + nbytes + 256,), fill, dtype=torch.uint8, device="cuda")
+    assert flat.data_ptr() % 256 == 0
+    lo, hi = 256 + off, 256 + off + nbytes
+
+    def check():
+        assert bool((flat[:lo] == fill).all()) and bool((flat[hi:] == fill).all()), "bytes outside the buffer were written"
+
+    return flat[lo:hi], check
+
+
+@pytest.mark.parametrize("L", [300, 37])
+def test_unaligned_buffers_and_strides(L):
+    """Input rows at byte offset 1 with a stride of cw1_bytes + 3, output rows at byte offset 1, fates at
+    byte offset 3: rows at every byte phase, and nothing outside the buffers is written."""
+    code1, code2 = PAIRS[0]
+    fl = flows(L, code1, code2)
+    grp = MessageWiseRelayGroup(L, code1, code2, fl.ns)
+    CW1, CW2, n = grp.cw1_bytes, grp.cw2_bytes, fl.total
+    ids = np.array([3, 0, 4], dtype=np.int32)
+    cuts = [0, 1, 1 + 97, 1 + 97 + 64, n]  # a one-packet burst, bursts of one and of several chunks
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        c = b - a
+        R = c * ids.size
+        er = np.concatenate([fl.pats[s][a:b] for s in ids])
+        rx = received(torch.cat([fl.cw1[s][a:b] for s in ids]), er)
+        buf, _ = carve(R * (CW1 + 3), 1, 0xA5)
+        rows = buf.as_strided((R, CW1), (CW1 + 3, 1), buf.storage_offset())
+        rows.copy_(rx)
+        assert rows.data_ptr() % 4 == 1 and rows.stride(0) == CW1 + 3
+        out, check_out = carve(R * CW2, 1, 0x5A)
+        ft, check_ft = carve(R, 3, 0x5A)
+        assert out.data_ptr() % 4 == 1 and ft.data_ptr() % 4 == 3
+        wl = torch.full((R,), -1, dtype=torch.int32, device="cuda")
+        grp.relay(ids, np.full(ids.size, c, dtype=np.int32), er, rows, out=out.view(R, CW2), out_len=wl, fate=ft)
+        torch.cuda.synchronize()
+        check_out()
+        check_ft()
+        for j, s in enumerate(ids):
+            r_cw, r_wl, r_ft = fl.ref[s]
+            sl = slice(j * c, (j + 1) * c)
+            assert torch.equal(ft[sl], r_ft[a:b]) and torch.equal(wl[sl], r_wl[a:b]), (s, a)
+            assert torch.equal(out.view(R, CW2)[sl], r_cw[a:b]), (s, a)
+
+
+def test_argument_errors_leave_the_group_unchanged():
+    L, (code1, code2) = 300, PAIRS[0]
+    fl = flows(L, code1, code2)
+    rng = np.random.default_rng(59)
+    grp = MessageWiseRelayGroup(L, code1, code2, fl.ns)
+    sent, got = drive(fl, grp, rng, cut_counts(code1, code2), upto=100)
+    before = [grp.state(s) for s in range(fl.ns)]
+    assert before == [(100, 100 - code1[0])] * fl.ns
+    CW1 = grp.cw1_bytes
+    bad = [(np.array([2, 2], dtype=np.int32), np.array([3, 3], dtype=np.int32), CW1),      # repeated id
+           (np.array([1, fl.ns], dtype=np.int32), np.array([3, 3], dtype=np.int32), CW1),  # id out of range
+           (np.array([1, -1], dtype=np.int32), np.array([3, 3], dtype=np.int32), CW1),
+           (np.array([1, 2], dtype=np.int32), np.array([6, 0], dtype=np.int32), CW1),      # a count of 0
+           (np.array([1, 2], dtype=np.int32), np.array([3, 3], dtype=np.int32), CW1 - 1)]  # cw1_stride < cw1_bytes
+    for b_ids, b_counts, width in bad:
+        rows = torch.zeros((6, width), dtype=torch.uint8, device="cuda")
+        with pytest.raises(fec.FecError) as e:
+            grp.relay(b_ids, b_counts, np.zeros(6, dtype=np.uint8), rows)
+        assert e.value.status == fec._lib.FEC_ERR_ARG
+        assert [grp.state(s) for s in range(fl.ns)] == before
+    drive(fl, grp, rng, cut_counts(code1, code2), sent=sent, got=got)
+    assert_equal(fl, grp, got)
+
+
+def test_end_to_end_through_a_second_lossy_hop():
+    """Relay rows through a second pattern into an ordinary (T2,B2,N2) stream group: the destination's rows
+    equal Codec(code2).decode of the reference frames, and a message arrives iff neither hop lost it."""
+    L, code1, code2 = 300, (10, 5, 2), (6, 2, 2)
+    (T1, _, _), (T2, B2, N2) = code1, code2
+    fl = flows(L, code1, code2)
+    ns = 3
+    rng = np.random.default_rng(61)
+    relay = MessageWiseRelayGroup(L, code1, code2, ns)
+    dest = fec.StreamGroup(L, T2, B2, N2, ns)
+    pats2 = [synthetic_pattern(T2, B2, N2, 11 * s)[:P] for s in range(ns)]
+    ids = np.arange(ns, dtype=np.int32)
+    outs, ols = [], []
+    for a in range(0, fl.total, 115):
+        b = min(a + 115, fl.total)
+        counts = np.full(ns, b - a, dtype=np.int32)
+        er = np.concatenate([fl.pats[s][a:b] for s in ids])
+        cw2, _, _ = relay.relay(ids, counts, er, received(torch.cat([fl.cw1[s][a:b] for s in ids]), er))
+        # hop-2 packets exist from hop-1 seq T1 on
+        lo = max(a, T1)
+        if lo >= b:
+            continue
+        keep = torch.cat([cw2[j * (b - a) + lo - a:(j + 1) * (b - a)] for j in range(ns)])
+        er2 = np.concatenate([pats2[s][lo - T1:b - T1] for s in ids])
+        o, ol = dest.decode_burst(ids, np.full(ns, b - lo, dtype=np.int32), er2, received(keep, er2))
+        outs.append(o.view(ns, b - lo, L))
+        ols.append(ol.view(ns, b - lo))
+    torch.cuda.synchronize()
+    out, ol = torch.cat(outs, dim=1), torch.cat(ols, dim=1)
+    c2 = codec(L, code2)
+    seen = set()
+    for s in range(ns):
+        r_cw, _, r_ft = fl.ref[s]
+        r_out, r_ol = c2.decode(r_cw[T1:].contiguous(), torch.from_numpy(pats2[s]).cuda())
+        assert torch.equal(ol[s, T2:], r_ol) and torch.equal(out[s, T2:], r_out), s
+        m = P - T2  # messages the destination has output
+        ok1 = (r_ft[T1:T1 + m] == 1) | (r_ft[T1:T1 + m] == 2)
+        f2 = torch.from_numpy(fec.plan_host(L, T2, B2, N2, pats2[s])).cuda()
+        ok2 = (f2 == 1) | (f2 == 2)
+        want_len = torch.where(ok1 & ok2, fl.len[s][:m], torch.zeros_like(fl.len[s][:m]))
+        col = torch.arange(L, device="cuda")[None, :]
+        want = torch.where(col < want_len[:, None], fl.pay[s][:m], torch.zeros_like(fl.pay[s][:m]))
+        assert torch.equal(ol[s, T2:], want_len) and torch.equal(out[s, T2:], want), s
+        seen |= {(bool(x), bool(y)) for x, y in zip(ok1.tolist(), ok2.tolist())}
+    assert {(True, True), (True, False), (False, True)} <= seen  # each hop alone loses messages the other keeps
