@@ -1,6 +1,7 @@
 // fec_burst.h -- what the burst kernels of the stream groups share (fec_streams.hip, fec_mw_relay_streams.hip):
-// a chunk's unit record, the decode row flags, exact division by a multiply, the fork-join pool for
-// the symbolic steps of a large call and the symbolic half of a burst (plan_burst_rows).
+// a chunk's unit record, the decode row flags, exact division by a multiply, the tuples the stream
+// kernels take (stream_tuple), the fork-join pool for the symbolic steps of a large call, the symbolic
+// half of a burst (plan_burst_rows) and of a whole decode call (DecodePlan).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,14 +12,18 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <thread>
 #include <vector>
 
 #include <pthread.h>
 #include <sched.h>
 
+#include "fec_group.h"
 #include "fec_host.h"
 
 namespace fec {
@@ -52,6 +57,18 @@ struct BurstUnit {   // one chunk = one workgroup
     int32_t pad;
 };
 constexpr uint8_t kRowClamp = 4, kRowErased = 8;  // decode row flags: fate | clamp | erased
+
+// One code (T,B,N) of a stream group at payload size L: false for a tuple that fec_codec_create or the
+// stream kernels (ring rows, registers, LDS tables) refuse.
+inline bool stream_tuple(int L, int T, int B, int N, Geometry* g) {
+    try {
+        *g = Geometry::make(L, T, B, N);
+    } catch (const std::invalid_argument&) {
+        return false;
+    }
+    if (g->L > 1500 || g->B < g->N || g->n > kMaxN - 1) return false;
+    return g->T + g->k <= kRR && g->k <= 16 && g->k * g->n <= 16 * 32;
+}
 
 }  // namespace
 }  // namespace fec
@@ -148,6 +165,15 @@ private:
 
 constexpr int kPoolMinItems = 1024;  // items per part below which a call steps on one thread
 
+// A group's pool (FEC_STREAMS_THREADS threads, default min(allowed CPUs - 1, 8)); null for a group too
+// small to ever fill two parts, or with one thread.
+std::unique_ptr<StepPool> make_step_pool(int nstreams) {
+    const int hw = allowed_cpus();  // not hardware_concurrency: the process's cpuset may be smaller
+    int nth = std::max(1, std::min(hw > 1 ? hw - 1 : 1, 8));
+    if (const char* e = std::getenv("FEC_STREAMS_THREADS")) nth = std::max(1, std::atoi(e));
+    return std::unique_ptr<StepPool>(nth > 1 && nstreams >= 2 * kPoolMinItems ? new StepPool(nth) : nullptr);
+}
+
 // The symbolic half of a burst for one stream: packets seq0 .. seq0 + count - 1 with erasure flags
 // er[]; one flag byte per row (the fate of packet seq - T | kRowClamp | kRowErased) and the k x n
 // blocks of the recovered rows, appended in row order.  A run of received packets on the fast path
@@ -171,5 +197,74 @@ void plan_burst_rows(fec::StreamPlanner& pl, int T, int kn, int64_t seq0, const 
         ++t;
     }
 }
+
+// The symbolic half of a decode call of M streams with R rows in all, and its records as the kernels
+// read them.  Streams are independent: contiguous parts of them, one per thread of the pool (a call of
+// fewer than 2 * kPoolMinItems rows: one part); a part's recovered rows keep their coefficient blocks
+// in row order, and a part's blocks follow those of the parts before it.
+template <class Unit>
+struct DecodePlan {
+    std::vector<Unit> units;
+    std::vector<uint8_t> flags;
+    std::vector<std::vector<uint8_t>> coefs;  // per part
+    size_t off_flags = 0, off_coef = 0, bytes = 0;  // staging: units | row flags | coefficient blocks
+
+    // tp(m): the chunk size of the call's m-th stream.  stream(m, row0, cnt, units, flags, coefs) plans
+    // that stream's cnt rows (plan_burst_rows), which start at row row0 of the call, appending to coefs,
+    // and fills its (cnt + tp - 1) / tp units, their coefficient offsets counted in coefs.
+    // rebase(unit, by) moves a unit's coefficient offsets by `by` bytes.  False: a step failed.
+    template <class Tp, class Stream, class Rebase>
+    bool plan(StepPool* pool, const int32_t* counts, int M, int64_t R, Tp tp, Stream stream, Rebase rebase) {
+        // (the pool calls every one of its parts: a call with fewer streams than parts leaves some empty)
+        const int np = (pool && R >= 2 * kPoolMinItems) ? pool->parts() : 1;
+        std::vector<int64_t> row_at(M + 1, 0), unit_at(M + 1, 0);
+        for (int m = 0; m < M; ++m) {
+            const int cnt = counts ? counts[m] : 1, t = tp(m);
+            row_at[m + 1] = row_at[m] + cnt;
+            unit_at[m + 1] = unit_at[m] + (cnt + t - 1) / t;
+        }
+        flags.resize(static_cast<size_t>(R));
+        units.resize(static_cast<size_t>(unit_at[M]));
+        coefs.resize(np);
+        auto first = [&](int p) { return static_cast<int>(static_cast<int64_t>(M) * p / np); };
+        std::atomic<bool> failed{false};
+        auto part = [&](int p) {
+            if (p < 0 || p >= np) return;
+            try {
+                for (int m = first(p); m < first(p + 1); ++m)
+                    stream(m, row_at[m], counts ? counts[m] : 1, units.data() + unit_at[m], flags.data() + row_at[m],
+                           coefs[p]);
+            } catch (...) {
+                failed.store(true);
+            }
+        };
+        if (np > 1)
+            pool->run(part);
+        else
+            part(0);
+        if (failed.load()) return false;
+        int64_t cbase = 0;
+        for (int p = 0; p < np; ++p) {
+            if (cbase)
+                for (int64_t ui = unit_at[first(p)]; ui < unit_at[first(p + 1)]; ++ui) rebase(units[ui], cbase);
+            cbase += static_cast<int64_t>(coefs[p].size());
+        }
+        off_flags = fec::align16(units.size() * sizeof(Unit));
+        off_coef = fec::align16(off_flags + flags.size());
+        bytes = off_coef + static_cast<size_t>(cbase) + 16;
+        return true;
+    }
+
+    // The records into a staging buffer of at least `bytes`.
+    void write(uint8_t* hs) const {
+        std::memcpy(hs, units.data(), units.size() * sizeof(Unit));
+        std::memcpy(hs + off_flags, flags.data(), flags.size());
+        uint8_t* c = hs + off_coef;
+        for (const auto& part : coefs) {
+            if (!part.empty()) std::memcpy(c, part.data(), part.size());
+            c += part.size();
+        }
+    }
+};
 
 }  // namespace

@@ -40,8 +40,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <atomic>
-#include <cstring>
 #include <memory>
 #include <new>
 #include <vector>
@@ -55,9 +53,6 @@
 
 namespace fec {
 namespace {
-
-constexpr int kMwTP = 32;            // packets per chunk, LDS permitting
-constexpr int kMwLds = 160 * 1024;   // a CU's LDS
 
 struct MwUnit {          // one chunk = one workgroup
     int64_t row0;        // its first row in the call's row arrays
@@ -357,8 +352,6 @@ __global__ __launch_bounds__(256) void fec_mw_relay_streams_kernel(MwArgs a) {
     write_rings(mt, 0);
 }
 
-constexpr size_t mw_align16(size_t v) { return (v + 15) & ~size_t(15); }
-
 // LDS carve-up for chunks of tp packets: fills the geometry but the pointers; returns its bytes
 int mw_lds(const Geometry& g1, const Geometry& g2, int tp, MwGeom* a) {
     a->L = g1.L, a->T1 = g1.T, a->k1 = g1.k, a->n1 = g1.n, a->CW1 = g1.CW;
@@ -377,17 +370,17 @@ int mw_lds(const Geometry& g1, const Geometry& g2, int tp, MwGeom* a) {
     a->PR = tp >= a->HR1 + a->H2 ? std::max({tp, a->H2, 1}) : tp;
     a->ROWS1 = a->HR1 + a->PR;
     a->ROWS2 = a->H2 + tp;
-    size_t off = mw_align16(static_cast<size_t>(std::max(1, g2.k * np2)) * 32);
+    size_t off = align16(static_cast<size_t>(std::max(1, g2.k * np2)) * 32);
     a->off_gf = static_cast<int>(off);
     off += 768;
     a->off_rows = static_cast<int>(off);
-    off = mw_align16(off + std::max(static_cast<size_t>(a->ROWS1) * a->CWS1, static_cast<size_t>(tp) * g2.CW + 32));
+    off = align16(off + std::max(static_cast<size_t>(a->ROWS1) * a->CWS1, static_cast<size_t>(tp) * g2.CW + 32));
     a->off_coef = static_cast<int>(off);
-    off = mw_align16(off + static_cast<size_t>(a->PR) * g1.k * g1.n + 16);
+    off = align16(off + static_cast<size_t>(a->PR) * g1.k * g1.n + 16);
     a->off_planes = static_cast<int>(off);
-    off = mw_align16(off + static_cast<size_t>(g2.k) * a->ROWS2 * a->SP2);
+    off = align16(off + static_cast<size_t>(g2.k) * a->ROWS2 * a->SP2);
     a->off_meta = static_cast<int>(off);
-    off = mw_align16(off + static_cast<size_t>(a->ROWS1) * 4 + static_cast<size_t>(a->PR) * 9);
+    off = align16(off + static_cast<size_t>(a->ROWS1) * 4 + static_cast<size_t>(a->PR) * 9);
     a->dk1 = fast_div(g1.k);
     a->dk2 = fast_div(g2.k);
     a->dns4 = fast_div(a->NS4);
@@ -396,25 +389,13 @@ int mw_lds(const Geometry& g1, const Geometry& g2, int tp, MwGeom* a) {
     return static_cast<int>(std::min<size_t>(off, 1u << 30));
 }
 
-// One hop's tuple as fec_streams_create takes it at this payload size (fec_codec_create's bounds, then
-// the stream kernels').
-bool mw_tuple(int L, int T, int B, int N, Geometry* g) {
-    try {
-        *g = Geometry::make(L, T, B, N);
-    } catch (const std::invalid_argument&) {
-        return false;
-    }
-    if (g->L > 1500 || g->B < g->N || g->n > kMaxN - 1) return false;
-    return g->T + g->k <= kRR && g->k <= 16 && g->k * g->n <= 16 * 32;
-}
-
-// The chunk of a burst cut in several: the most packets <= kMwTP whose LDS fits, at least the HR1 + H2
+// The chunk of a burst cut in several: the most packets <= kChunkTP whose LDS fits, at least the HR1 + H2
 // a later chunk needs in front of it.  0: not even that fits.
 int mw_fit(const Geometry& g1, const Geometry& g2, MwGeom* a, int* lds) {
     const int front = std::max(1, g1.T + g1.k - 1 + g2.n - 1);
-    for (int tp = kMwTP; tp >= front; --tp) {
+    for (int tp = kChunkTP; tp >= front; --tp) {
         *lds = mw_lds(g1, g2, tp, a);
-        if (*lds <= kMwLds) return tp;
+        if (*lds <= kCuLds) return tp;
     }
     return 0;
 }
@@ -431,29 +412,12 @@ struct fec_mw_relay_streams {
     std::shared_ptr<const fec::DecodeRules> rules;
     std::vector<std::unique_ptr<fec::StreamPlanner>> planners;
     std::vector<int64_t> seq;                // hop-1 packets fed so far per flow
-    std::vector<uint32_t> mark;              // duplicate-id check (call stamp per flow)
-    uint32_t stamp = 0;
     uint8_t* d_ring1 = nullptr;
     uint8_t* d_win2 = nullptr;
-    // Per-call records (chunks, row flags, coefficient blocks) go through a ring of pinned, mapped
-    // staging buffers that the kernel reads in place (as fec_streams'): a buffer is rewritten only
-    // after the kernel that read it.
-    static constexpr int kStageBufs = 4;
-    void* h_stage[kStageBufs] = {};
-    void* m_stage[kStageBufs] = {};
-    size_t stage_cap[kStageBufs] = {};
-    hipEvent_t staged[kStageBufs] = {};
-    int buf = 0;
-    hipEvent_t done = nullptr;               // the last call's kernel (rings)
-    bool poisoned = false;                   // a failed call left host and device state apart
+    fec::GroupStage stage;                   // per-call records: chunks, row flags, coefficient blocks
     ~fec_mw_relay_streams() {
-        for (hipEvent_t e : staged)
-            if (e) (void)hipEventDestroy(e);
-        if (done) (void)hipEventDestroy(done);
         for (void* p : {static_cast<void*>(d_ring1), static_cast<void*>(d_win2)})
             if (p) (void)hipFree(p);
-        for (void* p : h_stage)
-            if (p) (void)hipHostFree(p);
         if (c1) fec_codec_destroy(c1);
         if (c2) fec_codec_destroy(c2);
     }
@@ -461,56 +425,17 @@ struct fec_mw_relay_streams {
 
 namespace {
 
-int mw_stage_reserve(fec_mw_relay_streams* h, int b, size_t bytes) {
-    if (bytes <= h->stage_cap[b]) return FEC_OK;
-    const size_t cap = std::max(bytes, 2 * h->stage_cap[b]);
-    if (h->h_stage[b]) FEC_HIP(hipHostFree(h->h_stage[b]));
-    h->h_stage[b] = nullptr;
-    h->m_stage[b] = nullptr;
-    h->stage_cap[b] = 0;
-    FEC_HIP(hipHostMalloc(&h->h_stage[b], cap, hipHostMallocMapped));
-    FEC_HIP(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
-    h->stage_cap[b] = cap;
-    return FEC_OK;
-}
-
-// A launch with more than 64 KB of dynamic LDS needs the kernel's limit raised first.
-int mw_lds_allow(int lds) {
-    static std::mutex mu;
-    static int raised = 0;
-    std::lock_guard<std::mutex> lk(mu);
-    if (lds <= 64 * 1024 || lds <= raised) return FEC_OK;
-    FEC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(fec::fec_mw_relay_streams_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    raised = lds;
-    return FEC_OK;
-}
-
 int mw_relay_call(fec_mw_relay_streams* h, const int32_t* ids, const int32_t* counts, int M, const uint8_t* erasure,
                   const uint8_t* d_cw1, int64_t cw1_stride, uint8_t* d_cw2, int32_t* d_cw2_len, uint8_t* d_fate,
                   hipStream_t s) {
     if (M < 0 || M > h->nstreams) return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
     if (!ids || !erasure || !d_cw1 || !d_cw2 || !d_cw2_len || cw1_stride < h->g1.CW) return FEC_ERR_ARG;
-    int64_t R = M;
-    int maxc = 1;
-    if (counts) {
-        R = 0;
-        for (int m = 0; m < M; ++m) {
-            if (counts[m] < 1) return FEC_ERR_ARG;
-            R += counts[m];
-            maxc = std::max(maxc, counts[m]);
-        }
-    }
-    if (++h->stamp == 0) {
-        std::fill(h->mark.begin(), h->mark.end(), 0u);
-        h->stamp = 1;
-    }
-    for (int m = 0; m < M; ++m) {
-        const int id = ids[m];
-        if (id < 0 || id >= h->nstreams || h->mark[id] == h->stamp) return FEC_ERR_ARG;
-        h->mark[id] = h->stamp;
-    }
+    fec::GroupStage& stage = h->stage;
+    int64_t R = 0;
+    int maxc = 0;
+    if (int st = fec::check_counts(counts, M, &R, &maxc)) return st;
+    if (int st = stage.check_ids(ids, M)) return st;
     // bursts are one chunk each when the call's longest fits the chunk; else chunks of tpmax >= HR1 + H2
     const int tp = std::min(maxc, h->tpmax);
     fec::MwArgs a{};
@@ -518,101 +443,51 @@ int mw_relay_call(fec_mw_relay_streams* h, const int32_t* ids, const int32_t* co
     int64_t nu = 0;
     for (int m = 0; m < M; ++m) nu += ((counts ? counts[m] : 1) + tp - 1) / tp;
     if (nu > INT32_MAX) return FEC_ERR_ARG;
-    if (h->poisoned) return FEC_ERR_HIP;
-    // The symbolic decoders advance before the launch: a failure from here on leaves the host planners
-    // ahead of the device rings (or the staging ring in an unknown state), and the group refuses every
-    // later call.
-    struct Poison {
-        fec_mw_relay_streams* h;
-        bool armed = true;
-        ~Poison() { if (armed) h->poisoned = true; }
-    } poison{h};
-    if (int st = mw_lds_allow(lds)) return st;
-    // This call's staging buffer is free once the call that used it last has run; the previous call's
-    // kernel (the rings' last reader and writer) comes before this one's on any stream.
-    const int b = h->buf;
-    FEC_HIP(hipEventSynchronize(h->staged[b]));
-    FEC_HIP(hipStreamWaitEvent(s, h->done, 0));
+    static int lds_raised = 0;
+    if (int st = fec::lds_allow(reinterpret_cast<const void*>(fec::fec_mw_relay_streams_kernel), lds, &lds_raised))
+        return st;
+    if (int st = stage.begin(s)) return st;
+    fec::StageGuard guard{stage};  // the symbolic decoders advance before the launch
     const fec::Geometry& g1 = h->g1;
     const int kn1 = g1.k * g1.n, H2 = h->g2.n - 1;
-    // flows are independent: contiguous parts of them, one per thread; a flow's recovered rows keep their
-    // coefficient blocks in row order, so the blocks of any run of its rows are one range
-    const int np = (h->pool && R >= 2 * kPoolMinItems) ? h->pool->parts() : 1;
-    std::vector<int64_t> row_at(M + 1, 0), unit_at(M + 1, 0);
-    for (int m = 0; m < M; ++m) {
-        const int cnt = counts ? counts[m] : 1;
-        row_at[m + 1] = row_at[m] + cnt;
-        unit_at[m + 1] = unit_at[m] + (cnt + tp - 1) / tp;
-    }
-    std::vector<uint8_t> flags(static_cast<size_t>(R));
-    std::vector<fec::MwUnit> units(static_cast<size_t>(nu));
-    std::vector<std::vector<uint8_t>> coefs(np);
-    std::atomic<bool> failed{false};
-    auto part = [&](int p) {
-        if (p < 0 || p >= np) return;
-        try {
-            const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
-            const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
-            for (int m = m0; m < m1; ++m) {
-                const int id = ids[m], cnt = counts ? counts[m] : 1;
-                const int64_t seq = h->seq[id], base = static_cast<int64_t>(coefs[p].size());
-                const uint8_t* fr = flags.data() + row_at[m];
-                plan_burst_rows(*h->planners[id], g1.T, kn1, seq, erasure + row_at[m], cnt, flags.data() + row_at[m],
-                                coefs[p]);
-                // a chunk's blocks start with those of its first decoded row: H2 rows in front of a later chunk
-                int pos = 0;
-                int64_t rec = 0;
-                auto blocks_before = [&](int row) {
-                    for (; pos < row; ++pos) rec += (fr[pos] & 3) == fec::kRecovered;
-                    return base + rec * kn1;
-                };
-                fec::MwUnit* u = units.data() + unit_at[m];
-                for (int lead = 0; lead < cnt; lead += tp, ++u) {
-                    u->row0 = row_at[m] + lead;
-                    u->seq0 = seq + lead;
-                    u->coef = blocks_before(std::max(lead - H2, 0));
-                    u->tail_coef = 0;
-                    u->id = id;
-                    u->cnt = std::min(tp, cnt - lead);
-                    u->lead = lead;
-                    u->total = cnt;
-                }
-                if (cnt > tp) {  // the first chunk decodes the burst's last max(min(messages, H2), 1) rows again
-                    const int nmsg = cnt - static_cast<int>(std::min<int64_t>(std::max<int64_t>(g1.T - seq, 0), cnt));
-                    units[unit_at[m]].tail_coef = blocks_before(cnt - std::max(std::min(nmsg, H2), 1));
-                }
+    DecodePlan<fec::MwUnit> plan;
+    const bool ok = plan.plan(
+        h->pool.get(), counts, M, R, [tp](int) { return tp; },
+        [&](int m, int64_t row0, int cnt, fec::MwUnit* u, uint8_t* fl, std::vector<uint8_t>& coefs) {
+            const int id = ids[m];
+            const int64_t seq = h->seq[id], base = static_cast<int64_t>(coefs.size());
+            plan_burst_rows(*h->planners[id], g1.T, kn1, seq, erasure + row0, cnt, fl, coefs);
+            // a flow's recovered rows keep their blocks in row order, so the blocks of any run of its rows
+            // are one range; a chunk's start with those of its first decoded row: H2 rows in front of a
+            // later chunk
+            int pos = 0;
+            int64_t rec = 0;
+            auto blocks_before = [&](int row) {
+                for (; pos < row; ++pos) rec += (fl[pos] & 3) == fec::kRecovered;
+                return base + rec * kn1;
+            };
+            fec::MwUnit* first = u;
+            for (int lead = 0; lead < cnt; lead += tp, ++u) {
+                u->row0 = row0 + lead;
+                u->seq0 = seq + lead;
+                u->coef = blocks_before(std::max(lead - H2, 0));
+                u->tail_coef = 0;
+                u->id = id;
+                u->cnt = std::min(tp, cnt - lead);
+                u->lead = lead;
+                u->total = cnt;
             }
-        } catch (...) {
-            failed.store(true);
-        }
-    };
-    if (np > 1)
-        h->pool->run(part);
-    else
-        part(0);
-    if (failed.load()) return FEC_ERR_ARG;
-    // staging: units | row flags | coefficient blocks
-    const size_t off_flags = fec::mw_align16(static_cast<size_t>(nu) * sizeof(fec::MwUnit));
-    const size_t off_coef = fec::mw_align16(off_flags + static_cast<size_t>(R));
-    size_t ncoef = 0;
-    for (const auto& c : coefs) ncoef += c.size();
-    if (int st = mw_stage_reserve(h, b, off_coef + ncoef + 16)) return st;
-    uint8_t* hs = static_cast<uint8_t*>(h->h_stage[b]);
-    size_t cbase = 0;
-    for (int p = 0; p < np; ++p) {  // a part's blocks follow those of the parts before it
-        const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
-        const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
-        if (cbase)
-            for (int64_t ui = unit_at[m0]; ui < unit_at[m1]; ++ui) {
-                units[ui].coef += static_cast<int64_t>(cbase);
-                units[ui].tail_coef += static_cast<int64_t>(cbase);
+            if (cnt > tp) {  // the first chunk decodes the burst's last max(min(messages, H2), 1) rows again
+                const int nmsg = cnt - static_cast<int>(std::min<int64_t>(std::max<int64_t>(g1.T - seq, 0), cnt));
+                first->tail_coef = blocks_before(cnt - std::max(std::min(nmsg, H2), 1));
             }
-        if (!coefs[p].empty()) std::memcpy(hs + off_coef + cbase, coefs[p].data(), coefs[p].size());
-        cbase += coefs[p].size();
-    }
-    std::memcpy(hs, units.data(), units.size() * sizeof(fec::MwUnit));
-    std::memcpy(hs + off_flags, flags.data(), flags.size());
-    const uint8_t* rec = static_cast<const uint8_t*>(h->m_stage[b]);
+        },
+        [](fec::MwUnit& u, int64_t by) { u.coef += by, u.tail_coef += by; });
+    if (!ok) return FEC_ERR_ARG;
+    if (int st = stage.reserve(plan.bytes)) return st;
+    plan.write(stage.host());
+    const size_t off_flags = plan.off_flags, off_coef = plan.off_coef;
+    const uint8_t* rec = stage.device();
     fec::CodecView v1, v2;
     if (int st = fec::codec_view(h->c1, &v1)) return st;
     if (int st = fec::codec_view(h->c2, &v2)) return st;
@@ -630,12 +505,8 @@ int mw_relay_call(fec_mw_relay_streams* h, const int32_t* ids, const int32_t* co
     a.g.ptab = v2.ptab;
     hipLaunchKernelGGL(fec::fec_mw_relay_streams_kernel, dim3(static_cast<unsigned>(nu)), dim3(256),
                        static_cast<size_t>(lds), s, a);
-    FEC_HIP(hipGetLastError());
-    FEC_HIP(hipEventRecord(h->done, s));
-    FEC_HIP(hipEventRecord(h->staged[b], s));
-    h->buf = (b + 1) % fec_mw_relay_streams::kStageBufs;
+    if (int st = stage.commit(s)) return st;
     for (int m = 0; m < M; ++m) h->seq[ids[m]] += counts ? counts[m] : 1;
-    poison.armed = false;
     return FEC_OK;
 }
 
@@ -646,7 +517,7 @@ extern "C" {
 int fec_mw_relay_streams_fit(int max_payload, int T1, int B1, int N1, int T2, int B2, int N2, int* chunk_packets,
                              int* lds_bytes) {
     fec::Geometry g1, g2;
-    if (!fec::mw_tuple(max_payload, T1, B1, N1, &g1) || !fec::mw_tuple(max_payload, T2, B2, N2, &g2)) return FEC_ERR_ARG;
+    if (!fec::stream_tuple(max_payload, T1, B1, N1, &g1) || !fec::stream_tuple(max_payload, T2, B2, N2, &g2)) return FEC_ERR_ARG;
     fec::MwGeom a{};
     int lds = 0;
     const int tp = fec::mw_fit(g1, g2, &a, &lds);
@@ -664,7 +535,7 @@ int fec_mw_relay_streams_create(int max_payload, int T1, int B1, int N1, int T2,
     try {
         // everything that can refuse the arguments comes before the first allocation
         fec::Geometry g1, g2;
-        if (!fec::mw_tuple(max_payload, T1, B1, N1, &g1) || !fec::mw_tuple(max_payload, T2, B2, N2, &g2))
+        if (!fec::stream_tuple(max_payload, T1, B1, N1, &g1) || !fec::stream_tuple(max_payload, T2, B2, N2, &g2))
             return FEC_ERR_ARG;
         fec::MwGeom geo{};
         int lds = 0;
@@ -677,14 +548,8 @@ int fec_mw_relay_streams_create(int max_payload, int T1, int B1, int N1, int T2,
         h->rules = fec::shared_decode_rules(T1, B1, N1);
         h->planners.resize(nstreams);
         for (auto& p : h->planners) p.reset(new fec::StreamPlanner(g1, h->rules.get()));
-        {
-            const int hw = allowed_cpus();  // not hardware_concurrency: the process's cpuset may be smaller
-            int nth = std::max(1, std::min(hw > 1 ? hw - 1 : 1, 8));
-            if (const char* e = std::getenv("FEC_STREAMS_THREADS")) nth = std::max(1, std::atoi(e));
-            if (nth > 1 && nstreams >= 2 * kPoolMinItems) h->pool.reset(new StepPool(nth));
-        }
+        h->pool = make_step_pool(nstreams);
         h->seq.assign(nstreams, 0);
-        h->mark.assign(nstreams, 0);
         const size_t rb = static_cast<size_t>(nstreams) * fec::kRR * g1.CW;
         const size_t wb = static_cast<size_t>(nstreams) * geo.W2 * geo.SK2;
         FEC_HIP(hipMalloc(&h->d_ring1, rb));
@@ -692,13 +557,7 @@ int fec_mw_relay_streams_create(int max_payload, int T1, int B1, int N1, int T2,
         FEC_HIP(hipMalloc(&h->d_win2, wb));
         FEC_HIP(hipMemset(h->d_win2, 0, wb));
         const size_t stage = static_cast<size_t>(nstreams) * (sizeof(fec::MwUnit) + 1 + g1.k * g1.n + 16) + 64;
-        for (int b = 0; b < fec_mw_relay_streams::kStageBufs; ++b) {
-            if (int st = mw_stage_reserve(h.get(), b, stage)) return st;
-            FEC_HIP(hipEventCreateWithFlags(&h->staged[b], hipEventDisableTiming));
-            FEC_HIP(hipEventRecord(h->staged[b], nullptr));
-        }
-        FEC_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-        FEC_HIP(hipEventRecord(h->done, nullptr));
+        if (int st = h->stage.init(nstreams, stage)) return st;
         *out = h.release();
         return FEC_OK;
     } catch (const std::bad_alloc&) {

@@ -56,12 +56,12 @@
 
 #include <algorithm>
 #include <memory>
-#include <mutex>
 #include <new>
 #include <vector>
 
 #include "fec_amd.h"
 #include "fec_device.h"
+#include "fec_group.h"
 #include "fec_host.h"
 #include "fec_kernels.h"
 #include "fec_status.h"
@@ -71,7 +71,6 @@ namespace {
 
 constexpr int kRsThreads = 256;
 constexpr int kRsTP = 32;             // packets per chunk, LDS permitting
-constexpr int kRsLds = 160 * 1024;    // a CU's LDS
 constexpr int kRsMaxD = 64;           // decoded packets of a chunk: n2-1 + TP <= 16 + 32; rows: H + TP <= 64
 constexpr int kRsMaxCodes = 64;       // tuples of a mixed group
 constexpr int kRsRuleU16 = 16 + 16 * 17;  // a wave's rule: sel[k], log col[k][n]
@@ -362,8 +361,6 @@ __global__ __launch_bounds__(kRsThreads) __attribute__((amdgpu_waves_per_eu(6)))
                     a.r.ring + static_cast<int64_t>(u.id) * a.slot, a.out_stride);
 }
 
-constexpr size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
-
 // every chunk's rows and decoded packets have a place in the fixed part: H <= n1+n2-2, chunks <= kRsTP
 static_assert(2 * kMaxRuleN - 2 + kRsTP <= kRsMaxD, "LDS carve-up");
 
@@ -399,7 +396,7 @@ RsGeom rs_side(bool relay, int max_payload, int T1, int N1, int T2, int N2) {
     // a burst of more than one chunk takes chunks of at least H packets (the rows in front of a
     // later chunk all lie in the burst); the smallest chunk is one packet of a one-packet call
     for (int tp = kRsTP; tp >= s.H && !s.tpmax; --tp)
-        if (rs_lds(s, tp) <= static_cast<size_t>(kRsLds)) s.tpmax = tp;
+        if (rs_lds(s, tp) <= static_cast<size_t>(kCuLds)) s.tpmax = tp;
     return s;
 }
 
@@ -444,28 +441,12 @@ struct fec_relay_streams {
     int nstreams = 0;
     bool mixed = false;                      // made by fec_relay_streams_create_mixed: the table-driven kernels
     std::vector<int32_t> code_of;            // per stream
-    std::vector<uint32_t> mark;              // duplicate-id check (call stamp per stream)
-    uint32_t stamp = 0;
     std::vector<uint64_t> next_hist;         // a call's new flag registers, committed after the launch
-    // Per-call records (chunks + masks) go through a ring of pinned, mapped staging buffers that the
-    // kernels read in place (as fec_streams'): a buffer is rewritten only after the kernel that read it.
-    static constexpr int kStageBufs = 4;
-    void* h_stage[kStageBufs] = {};
-    void* m_stage[kStageBufs] = {};
-    size_t stage_cap[kStageBufs] = {};
-    hipEvent_t staged[kStageBufs] = {};
-    int buf = 0;
-    hipEvent_t done = nullptr;               // the last call's kernel (rings)
-    bool poisoned = false;                   // a failed call left host and device state apart
+    fec::GroupStage stage;                   // per-call records: chunks + masks
     ~fec_relay_streams() {
-        for (hipEvent_t e : staged)
-            if (e) (void)hipEventDestroy(e);
-        if (done) (void)hipEventDestroy(done);
         for (void* p : {static_cast<void*>(relay.d_ring), static_cast<void*>(dest.d_ring),
                         static_cast<void*>(relay.d_codes), static_cast<void*>(dest.d_codes)})
             if (p) (void)hipFree(p);
-        for (void* p : h_stage)
-            if (p) (void)hipHostFree(p);
         for (Hop& hp : hops) {
             if (hp.d_tab) (void)hipFree(hp.d_tab);
             if (hp.codec) fec_codec_destroy(hp.codec);
@@ -475,29 +456,6 @@ struct fec_relay_streams {
 
 namespace {
 
-int rs_stage_reserve(fec_relay_streams* h, int b, size_t bytes) {
-    if (bytes <= h->stage_cap[b]) return FEC_OK;
-    const size_t cap = std::max(bytes, 2 * h->stage_cap[b]);
-    if (h->h_stage[b]) FEC_HIP(hipHostFree(h->h_stage[b]));
-    h->h_stage[b] = nullptr;
-    h->m_stage[b] = nullptr;
-    h->stage_cap[b] = 0;
-    FEC_HIP(hipHostMalloc(&h->h_stage[b], cap, hipHostMallocMapped));
-    FEC_HIP(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
-    h->stage_cap[b] = cap;
-    return FEC_OK;
-}
-
-// A launch with more than 64 KB of dynamic LDS needs the kernel's limit raised first.
-int rs_lds_allow(const void* kernel, int lds, int* raised) {
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    if (lds <= 64 * 1024 || lds <= *raised) return FEC_OK;
-    FEC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    *raised = lds;
-    return FEC_OK;
-}
-
 // One side's call.  in: R rows of in_stride bytes; out: R rows of the side's out_stride.  A stream's
 // geometry and chunk size are its code's (one code: a constant).
 template <bool RELAY>
@@ -506,25 +464,11 @@ int rs_call(fec_relay_streams* h, fec_relay_streams::Side& sd, const int32_t* id
     if (M < 0 || M > h->nstreams) return FEC_ERR_ARG;
     if (M == 0) return FEC_OK;
     if (!ids || !erasure || !in || !out || in_stride < sd.in_min) return FEC_ERR_ARG;
-    int64_t R = M;
-    int maxc = 1;
-    if (counts) {
-        R = 0;
-        for (int m = 0; m < M; ++m) {
-            if (counts[m] < 1) return FEC_ERR_ARG;
-            R += counts[m];
-            maxc = std::max(maxc, counts[m]);
-        }
-    }
-    if (++h->stamp == 0) {
-        std::fill(h->mark.begin(), h->mark.end(), 0u);
-        h->stamp = 1;
-    }
-    for (int m = 0; m < M; ++m) {
-        const int id = ids[m];
-        if (id < 0 || id >= h->nstreams || h->mark[id] == h->stamp) return FEC_ERR_ARG;
-        h->mark[id] = h->stamp;
-    }
+    fec::GroupStage& stage = h->stage;
+    int64_t R = 0;
+    int maxc = 0;
+    if (int st = fec::check_counts(counts, M, &R, &maxc)) return st;
+    if (int st = stage.check_ids(ids, M)) return st;
     // A code's bursts are one chunk each when the call's longest burst fits its chunk; else chunks of
     // tpmax >= H.  The launch takes the LDS of the largest chunk among the codes present in the call.
     int tp_of[fec::kRsMaxCodes];
@@ -541,26 +485,16 @@ int rs_call(fec_relay_streams* h, fec_relay_streams::Side& sd, const int32_t* id
         nu += ((counts ? counts[m] : 1) + tp_of[c] - 1) / tp_of[c];
     }
     if (nu > INT32_MAX) return FEC_ERR_ARG;
-    if (h->poisoned) return FEC_ERR_HIP;
-    // From here on a failure may leave the staging ring or the events in an unknown state.
-    struct Poison {
-        fec_relay_streams* h;
-        bool armed = true;
-        ~Poison() { if (armed) h->poisoned = true; }
-    } poison{h};
     const void* kern = h->mixed ? reinterpret_cast<const void*>(fec::fec_relay_streams_mixed_kernel<RELAY>)
                                 : reinterpret_cast<const void*>(fec::fec_relay_streams_kernel<RELAY>);
     static int lds_raised[2] = {0, 0};  // per kernel (of this template instance), not per group
-    if (int st = rs_lds_allow(kern, lds, &lds_raised[h->mixed])) return st;
-    // This call's staging buffer is free once the call that used it last has run; the previous
-    // call's kernel (the rings' last reader and writer) comes before this one's on any stream.
-    const int b = h->buf;
-    FEC_HIP(hipEventSynchronize(h->staged[b]));
-    FEC_HIP(hipStreamWaitEvent(s, h->done, 0));
+    if (int st = fec::lds_allow(kern, lds, &lds_raised[h->mixed])) return st;
+    if (int st = stage.begin(s)) return st;
+    fec::StageGuard guard{stage};
     const size_t off_masks = fec::align16(static_cast<size_t>(nu) * sizeof(fec::RsUnit));
-    if (int st = rs_stage_reserve(h, b, off_masks + static_cast<size_t>(R) * 4)) return st;
-    fec::RsUnit* un = static_cast<fec::RsUnit*>(h->h_stage[b]);
-    uint32_t* masks = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(h->h_stage[b]) + off_masks);
+    if (int st = stage.reserve(off_masks + static_cast<size_t>(R) * 4)) return st;
+    fec::RsUnit* un = reinterpret_cast<fec::RsUnit*>(stage.host());
+    uint32_t* masks = reinterpret_cast<uint32_t*>(stage.host() + off_masks);
     int64_t row = 0;
     for (int m = 0; m < M; ++m) {
         const int id = ids[m], cnt = counts ? counts[m] : 1, c = h->code_of[id], tp = tp_of[c];
@@ -581,7 +515,7 @@ int rs_call(fec_relay_streams* h, fec_relay_streams::Side& sd, const int32_t* id
         }
         row += cnt;
     }
-    const uint8_t* rec = static_cast<const uint8_t*>(h->m_stage[b]);
+    const uint8_t* rec = stage.device();
     fec::RsRows r{};
     r.in = in;
     r.in_stride = in_stride;
@@ -598,15 +532,11 @@ int rs_call(fec_relay_streams* h, fec_relay_streams::Side& sd, const int32_t* id
         const fec::RsArgs a{r, sd.geo[0], static_cast<int>(fec::rs_off_ct(sd.geo[0], tp_of[0]))};
         hipLaunchKernelGGL(fec::fec_relay_streams_kernel<RELAY>, grid, block, static_cast<size_t>(lds), s, a);
     }
-    FEC_HIP(hipGetLastError());
-    FEC_HIP(hipEventRecord(h->done, s));
-    FEC_HIP(hipEventRecord(h->staged[b], s));
-    h->buf = (b + 1) % fec_relay_streams::kStageBufs;
+    if (int st = stage.commit(s)) return st;
     for (int m = 0; m < M; ++m) {
         sd.seq[ids[m]] += counts ? counts[m] : 1;
         sd.hist[ids[m]] = h->next_hist[m];
     }
-    poison.armed = false;
     return FEC_OK;
 }
 
@@ -693,16 +623,9 @@ int rs_create(int max_payload, const int32_t* tuples, int ncodes, const int32_t*
         h->dest.geo = std::move(dg);
         if (int st = rs_create_side(h->relay, nstreams, mixed)) return st;
         if (int st = rs_create_side(h->dest, nstreams, mixed)) return st;
-        h->mark.assign(nstreams, 0);
         h->next_hist.assign(nstreams, 0);
         const size_t stage = static_cast<size_t>(nstreams) * (sizeof(fec::RsUnit) + 4) + 64;
-        for (int b = 0; b < fec_relay_streams::kStageBufs; ++b) {
-            if (int st = rs_stage_reserve(h.get(), b, stage)) return st;
-            FEC_HIP(hipEventCreateWithFlags(&h->staged[b], hipEventDisableTiming));
-            FEC_HIP(hipEventRecord(h->staged[b], nullptr));
-        }
-        FEC_HIP(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-        FEC_HIP(hipEventRecord(h->done, nullptr));
+        if (int st = h->stage.init(nstreams, stage)) return st;
         *out = h.release();
         return FEC_OK;
     } catch (const std::bad_alloc&) {

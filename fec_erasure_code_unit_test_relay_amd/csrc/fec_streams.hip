@@ -23,20 +23,10 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <memory>
-#include <mutex>
 #include <new>
-#include <thread>
 #include <vector>
-
-#include <pthread.h>
-#include <sched.h>
 
 #include "fec_amd.h"
 #include "fec_burst.h"
@@ -738,30 +728,15 @@ struct fec_streams {
     std::shared_ptr<const fec::DecodeRules> rules;
     std::vector<std::unique_ptr<fec::StreamPlanner>> planners;
     std::vector<int64_t> enc_seq, dec_seq;   // packets sent / received so far per stream
-    std::vector<uint32_t> mark;              // duplicate-id check (call stamp per stream)
-    uint32_t stamp = 0;
     uint8_t* d_win = nullptr;                // encoder windows
     uint8_t* d_ring = nullptr;               // decoder rings
-    // Per-call records (ids + seqs / items + coefs) go through a ring of kStageBufs staging buffers,
-    // so the host prepares a call (the decoders' symbolic steps) while the GPU still runs the ones
-    // before it; a buffer is rewritten only after its upload has completed.
-    static constexpr int kStageBufs = 4;
-    // The kernels read the records straight from the pinned buffers (mapped: m_stage) -- an upload
-    // per call put an SDMA copy and its hand-off to the kernel on the GPU's path, twice per
-    // encode + decode pair (FEC_STREAMS_UPLOAD=1 keeps those uploads into d_stage).
-    void* d_stage[kStageBufs] = {};
-    void* h_stage[kStageBufs] = {};          // pinned records
-    void* m_stage[kStageBufs] = {};          // their device addresses
-    bool upload = false;
-    hipEvent_t staged[kStageBufs] = {};      // the last kernel (and upload) that read h_stage[b]
-    int buf = 0;                             // the next call's buffer
-    size_t stage_bytes = 0;
-    size_t stage_cap[kStageBufs] = {};       // bytes of h_stage[b] (a burst call grows its buffer to its records)
-    hipEvent_t done = nullptr;               // the last call's kernel (windows, rings, older d_stage free)
-    bool poisoned = false;                   // a failed call left host and device state apart
+    // Per-call records (ids + seqs / items + coefs / chunks + flags + coefs).  The kernels read them
+    // straight from the pinned buffers: an upload per call put an SDMA copy and its hand-off to the
+    // kernel on the GPU's path, twice per encode + decode pair.
+    fec::GroupStage stage;
     // Mixed groups (fec_streams_create_mixed; empty otherwise, and then codec / g / W / SK / rules above
     // are unused): the codes, each stream's code, the uniform row and slot strides, and the kernels'
-    // per-code tables.  A code's chunk sizes are fixed at create (for bursts of kBurstTP or more).
+    // per-code tables.  A code's chunk sizes are fixed at create (for bursts of kChunkTP or more).
     struct Code {
         fec_codec* codec = nullptr;
         fec::Geometry g;
@@ -779,97 +754,16 @@ struct fec_streams {
             if (c.codec) fec_codec_destroy(c.codec);
         for (void* p : {static_cast<void*>(d_enc_codes), static_cast<void*>(d_dec_codes)})
             if (p) (void)hipFree(p);
-        for (hipEvent_t e : staged)
-            if (e) (void)hipEventDestroy(e);
-        if (done) (void)hipEventDestroy(done);
         for (void* p : {static_cast<void*>(d_win), static_cast<void*>(d_ring)})
             if (p) (void)hipFree(p);
-        for (void* p : d_stage)
-            if (p) (void)hipFree(p);
-        for (void* p : h_stage)
-            if (p) (void)hipHostFree(p);
         if (codec) fec_codec_destroy(codec);
     }
 };
 
 namespace {
 
-#define FS_TRY(expr)                              \
-    do {                                          \
-        FEC_HIP((expr)); \
-    } while (0)
-
-// ids distinct and in range
-int check_ids(fec_streams* h, const int32_t* ids, int M) {
-    if (++h->stamp == 0) {
-        std::fill(h->mark.begin(), h->mark.end(), 0u);
-        h->stamp = 1;
-    }
-    for (int m = 0; m < M; ++m) {
-        const int id = ids[m];
-        if (id < 0 || id >= h->nstreams || h->mark[id] == h->stamp) return FEC_ERR_ARG;
-        h->mark[id] = h->stamp;
-    }
-    return FEC_OK;
-}
-
-// This call's staging buffer: the call that used it before has read it (host wait on that call's
-// kernel, kStageBufs calls back), and the previous call's kernel -- which read / wrote the windows and
-// rings, after every older kernel and so after the last reader of d_stage[b] -- comes before
-// anything this call enqueues on `s`, whichever stream the previous call used (device-side wait).
-int stage_free(fec_streams* h, hipStream_t s, int* b) {
-    if (h->poisoned) return FEC_ERR_HIP;
-    *b = h->buf;
-    FS_TRY(hipEventSynchronize(h->staged[*b]));
-    FS_TRY(hipStreamWaitEvent(s, h->done, 0));
-    return FEC_OK;
-}
-
-
-// Staging buffer b (free: stage_free has waited for its last reader) holds at least `bytes`.
-int stage_reserve(fec_streams* h, int b, size_t bytes) {
-    if (bytes <= h->stage_cap[b]) return FEC_OK;
-    const size_t cap = std::max(bytes, 2 * h->stage_cap[b]);
-    if (h->d_stage[b]) {
-        FS_TRY(hipFree(h->d_stage[b]));
-        h->d_stage[b] = nullptr;
-    }
-    FS_TRY(hipHostFree(h->h_stage[b]));
-    h->h_stage[b] = nullptr;
-    h->m_stage[b] = nullptr;
-    h->stage_cap[b] = 0;
-    if (h->upload) FS_TRY(hipMalloc(&h->d_stage[b], cap));
-    FS_TRY(hipHostMalloc(&h->h_stage[b], cap, hipHostMallocMapped));
-    FS_TRY(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
-    h->stage_cap[b] = cap;
-    return FEC_OK;
-}
-
-constexpr int kBurstLds = 160 * 1024;  // dynamic LDS a burst kernel may take (a CU's whole LDS)
-constexpr int kBurstTP = 32;          // packets per chunk, LDS permitting (at least the packets a chunk needs in front)
-constexpr size_t align16(size_t v) { return (v + 15) & ~size_t(15); }
-
-// A launch with more than 64 KB of dynamic LDS needs the kernel's limit raised first (once per size).
-int burst_lds_allow(const void* kernel, int lds, int* raised) {
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    if (lds <= 64 * 1024 || lds <= *raised) return FEC_OK;
-    FS_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    *raised = lds;
-    return FEC_OK;
-}
-
-// counts all >= 1; their sum and largest
-int check_counts(const int32_t* counts, int M, int64_t* R, int* maxc) {
-    *R = 0;
-    *maxc = 0;
-    for (int m = 0; m < M; ++m) {
-        if (counts[m] < 1) return FEC_ERR_ARG;
-        *R += counts[m];
-        *maxc = std::max(*maxc, counts[m]);
-    }
-    return FEC_OK;
-}
+using fec::align16;
+using fec::check_counts;
 
 // LDS carve-up of burst_encode_chunk for chunks of tp packets: fills the geometry but ptab; returns its bytes
 int burst_enc_lds(const fec::Geometry& g, int tp, fec::BurstEncGeom* a) {
@@ -919,16 +813,16 @@ int burst_dec_lds(const fec::Geometry& g, int tp, fec::BurstDecGeom* a) {
     return static_cast<int>(std::min<size_t>(off, 1u << 30));
 }
 
-// Packets per chunk for a call whose longest burst has maxc packets: at most kBurstTP (or maxc), at
+// Packets per chunk for a call whose longest burst has maxc packets: at most kChunkTP (or maxc), at
 // least `front` (the packets a chunk needs in front of it, so that only a burst's first chunk reads
-// the ring), and within kBurstLds.  0: this geometry does not fit.
+// the ring), and within kCuLds.  0: this geometry does not fit.
 template <class Geom, class F>
 int burst_chunk(const fec::Geometry& g, int maxc, int front, F lds_of, Geom* a, int* lds) {
     if (g.S * g.k > 16384 || g.CW > 16384) return 0;
     const int lo = std::max(1, front);
-    for (int tp = std::max(lo, std::min(maxc, kBurstTP)); tp >= lo; --tp) {
+    for (int tp = std::max(lo, std::min(maxc, fec::kChunkTP)); tp >= lo; --tp) {
         *lds = lds_of(g, tp, a);
-        if (*lds <= kBurstLds) return tp;
+        if (*lds <= fec::kCuLds) return tp;
     }
     return 0;
 }
@@ -953,32 +847,14 @@ fec::BurstUnit* burst_fill_units(fec::BurstUnit* u, int id, int code, int count,
 // counters, zeroed windows (wb bytes) and rings (rb bytes), the staging buffers and the events.
 int group_state_init(fec_streams* h, size_t wb, size_t rb, size_t stage_bytes) {
     const int nstreams = h->nstreams;
-    {
-        const int hw = allowed_cpus();  // not hardware_concurrency: the process's cpuset may be smaller
-        int nth = std::max(1, std::min(hw > 1 ? hw - 1 : 1, 8));
-        if (const char* e = std::getenv("FEC_STREAMS_THREADS")) nth = std::max(1, std::atoi(e));
-        if (nth > 1 && nstreams >= 2 * kPoolMinItems) h->pool.reset(new StepPool(nth));
-    }
+    h->pool = make_step_pool(nstreams);
     h->enc_seq.assign(nstreams, 0);
     h->dec_seq.assign(nstreams, 0);
-    h->mark.assign(nstreams, 0);
-    FS_TRY(hipMalloc(&h->d_win, wb));
-    FS_TRY(hipMemset(h->d_win, 0, wb));
-    FS_TRY(hipMalloc(&h->d_ring, rb));
-    FS_TRY(hipMemset(h->d_ring, 0, rb));
-    h->stage_bytes = stage_bytes;
-    if (const char* e = std::getenv("FEC_STREAMS_UPLOAD")) h->upload = std::atoi(e) != 0;
-    for (int b = 0; b < fec_streams::kStageBufs; ++b) {
-        if (h->upload) FS_TRY(hipMalloc(&h->d_stage[b], h->stage_bytes));
-        FS_TRY(hipHostMalloc(&h->h_stage[b], h->stage_bytes, hipHostMallocMapped));
-        FS_TRY(hipHostGetDevicePointer(&h->m_stage[b], h->h_stage[b], 0));
-        h->stage_cap[b] = h->stage_bytes;
-        FS_TRY(hipEventCreateWithFlags(&h->staged[b], hipEventDisableTiming));
-        FS_TRY(hipEventRecord(h->staged[b], nullptr));
-    }
-    FS_TRY(hipEventCreateWithFlags(&h->done, hipEventDisableTiming));
-    FS_TRY(hipEventRecord(h->done, nullptr));
-    return FEC_OK;
+    FEC_HIP(hipMalloc(&h->d_win, wb));
+    FEC_HIP(hipMemset(h->d_win, 0, wb));
+    FEC_HIP(hipMalloc(&h->d_ring, rb));
+    FEC_HIP(hipMemset(h->d_ring, 0, rb));
+    return h->stage.init(nstreams, stage_bytes);
 }
 
 // ---- mixed groups ------------------------------------------------------------------------------
@@ -986,7 +862,7 @@ int group_state_init(fec_streams* h, size_t wb, size_t rb, size_t stage_bytes) {
 constexpr int kMaxCodes = 64;
 
 // One code of a mixed group at payload size L: its geometry and its burst chunks, fixed for bursts of
-// kBurstTP or more, through the routines the one-code calls use.  FEC_ERR_ARG: a tuple that
+// kChunkTP or more, through the routines the one-code calls use.  FEC_ERR_ARG: a tuple that
 // fec_streams_create refuses (fec_codec_create's bounds, then the stream kernels'), or whose smallest
 // chunk does not fit the LDS.
 struct CodeFit {
@@ -996,18 +872,12 @@ struct CodeFit {
     fec::BurstDecGeom dec;
 };
 int mixed_code_fit(int L, const int32_t* tbn, CodeFit* f) {
-    try {
-        f->g = fec::Geometry::make(L, tbn[0], tbn[1], tbn[2]);
-    } catch (const std::invalid_argument&) {
-        return FEC_ERR_ARG;
-    }
+    if (!fec::stream_tuple(L, tbn[0], tbn[1], tbn[2], &f->g)) return FEC_ERR_ARG;
     const fec::Geometry& g = f->g;
-    if (g.L > 1500 || g.B < g.N || g.n > fec::kMaxN - 1) return FEC_ERR_ARG;
-    if (g.T + g.k > fec::kRR || g.k > 16 || g.k * g.n > 16 * 32) return FEC_ERR_ARG;
     f->enc = fec::BurstEncGeom{};
     f->dec = fec::BurstDecGeom{};
-    f->enc_tp = burst_chunk(g, kBurstTP, g.n - 1, burst_enc_lds, &f->enc, &f->enc_lds);
-    f->dec_tp = burst_chunk(g, kBurstTP, g.T + g.k - 1, burst_dec_lds, &f->dec, &f->dec_lds);
+    f->enc_tp = burst_chunk(g, fec::kChunkTP, g.n - 1, burst_enc_lds, &f->enc, &f->enc_lds);
+    f->dec_tp = burst_chunk(g, fec::kChunkTP, g.T + g.k - 1, burst_dec_lds, &f->dec, &f->dec_lds);
     return f->enc_tp && f->dec_tp ? FEC_OK : FEC_ERR_ARG;
 }
 
@@ -1042,7 +912,8 @@ int64_t chunk_count(const fec_streams* h, bool enc, const ChunkCode& one, const 
 // The encode half of a chunk call; counts (null: all 1) are checked, the largest is maxc.
 int encode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, int maxc, const uint8_t* d_payload,
                   const int32_t* d_payload_len, uint8_t* d_codeword, int32_t* d_codeword_len, hipStream_t s) {
-    if (int st = check_ids(h, ids, M)) return st;
+    fec::GroupStage& stage = h->stage;
+    if (int st = stage.check_ids(ids, M)) return st;
     const bool mixed = !h->codes.empty();
     fec::BurstEncArgs a1;  // a one-code group's arguments: its geometry
     ChunkCode one{};
@@ -1057,15 +928,11 @@ int encode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int
     static int lds_raised[2] = {0, 0};  // per kernel
     const void* kernel = mixed ? reinterpret_cast<const void*>(fec::fec_streams_encode_mixed_kernel)
                                : reinterpret_cast<const void*>(fec::fec_streams_encode_burst_kernel);
-    if (int st = burst_lds_allow(kernel, lds, &lds_raised[mixed])) return st;
-    int b = 0;
-    if (int st = stage_free(h, s, &b)) return st;
-    const size_t bytes = static_cast<size_t>(nu) * sizeof(fec::BurstUnit);
-    if (int st = stage_reserve(h, b, bytes)) {
-        h->poisoned = true;  // the buffer may be gone
-        return st;
-    }
-    fec::BurstUnit* u = static_cast<fec::BurstUnit*>(h->h_stage[b]);
+    if (int st = fec::lds_allow(kernel, lds, &lds_raised[mixed])) return st;
+    if (int st = stage.begin(s)) return st;
+    fec::StageGuard guard{stage};
+    if (int st = stage.reserve(static_cast<size_t>(nu) * sizeof(fec::BurstUnit))) return st;
+    fec::BurstUnit* u = reinterpret_cast<fec::BurstUnit*>(stage.host());
     int64_t row = 0;
     for (int m = 0; m < M; ++m) {
         const int id = ids[m], cnt = counts ? counts[m] : 1;
@@ -1073,9 +940,8 @@ int encode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int
         u = burst_fill_units(u, id, c.code, cnt, row, c.tp, h->enc_seq[id]);
         row += cnt;
     }
-    if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
     const fec::BurstEncRows rows{d_payload, d_payload_len, d_codeword, d_codeword_len};
-    const fec::BurstUnit* du = static_cast<const fec::BurstUnit*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
+    const fec::BurstUnit* du = reinterpret_cast<const fec::BurstUnit*>(stage.device());
     const dim3 grid(static_cast<unsigned>(nu));
     if (mixed) {
         const fec::MixedEncArgs a{rows, du, h->d_win, h->d_enc_codes};
@@ -1086,10 +952,7 @@ int encode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int
         a1.rows = rows, a1.units = du, a1.win = h->d_win, a1.g.ptab = v.ptab;
         hipLaunchKernelGGL(fec::fec_streams_encode_burst_kernel, grid, dim3(256), lds, s, a1);
     }
-    FS_TRY(hipGetLastError());
-    FS_TRY(hipEventRecord(h->done, s));
-    FS_TRY(hipEventRecord(h->staged[b], s));
-    h->buf = (b + 1) % fec_streams::kStageBufs;
+    if (int st = stage.commit(s)) return st;
     for (int m = 0; m < M; ++m) h->enc_seq[ids[m]] += counts ? counts[m] : 1;
     return FEC_OK;
 }
@@ -1098,7 +961,8 @@ int encode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int
 int decode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int M, int64_t R, int maxc,
                   const uint8_t* erasure, const uint8_t* d_codeword, uint8_t* d_payload_out, int32_t* d_payload_len,
                   hipStream_t s) {
-    if (int st = check_ids(h, ids, M)) return st;
+    fec::GroupStage& stage = h->stage;
+    if (int st = stage.check_ids(ids, M)) return st;
     const bool mixed = !h->codes.empty();
     fec::BurstDecArgs a1;  // a one-code group's arguments: its geometry
     ChunkCode one{};
@@ -1113,82 +977,32 @@ int decode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int
     static int lds_raised[2] = {0, 0};  // per kernel
     const void* kernel = mixed ? reinterpret_cast<const void*>(fec::fec_streams_decode_mixed_kernel)
                                : reinterpret_cast<const void*>(fec::fec_streams_decode_burst_kernel);
-    if (int st = burst_lds_allow(kernel, lds, &lds_raised[mixed])) return st;
-    int b = 0;
-    if (int st = stage_free(h, s, &b)) return st;
-    // The symbolic decoders advance before the launch: a failure from here on leaves the host planners
-    // ahead of the device rings, and the group refuses every later call.
-    struct Poison {
-        fec_streams* h;
-        bool armed = true;
-        ~Poison() { if (armed) h->poisoned = true; }
-    } poison{h};
+    if (int st = fec::lds_allow(kernel, lds, &lds_raised[mixed])) return st;
+    if (int st = stage.begin(s)) return st;
+    fec::StageGuard guard{stage};  // the symbolic decoders advance before the launch
     try {
-        // streams are independent: contiguous parts of them, one per thread; a part's recovered rows
-        // keep their coefficient blocks in row order
-        // (the pool calls every one of its parts: a call with fewer streams than parts leaves some empty)
-        const int np = (h->pool && R >= 2 * kPoolMinItems) ? h->pool->parts() : 1;
-        std::vector<int64_t> row_at(M + 1, 0), unit_at(M + 1, 0);
-        for (int m = 0; m < M; ++m) {
-            const int cnt = counts ? counts[m] : 1, tp = chunk_code(h, false, one, ids[m]).tp;
-            row_at[m + 1] = row_at[m] + cnt;
-            unit_at[m + 1] = unit_at[m] + (cnt + tp - 1) / tp;
-        }
-        std::vector<uint8_t> flags(static_cast<size_t>(R));
-        std::vector<fec::BurstUnit> units(static_cast<size_t>(nu));
-        std::vector<std::vector<uint8_t>> coefs(np);
-        std::atomic<bool> failed{false};
-        auto part = [&](int p) {
-            if (p < 0 || p >= np) return;
-            try {
-                const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
-                const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
-                int64_t cbytes = 0;  // coefficient bytes of this part's chunks so far
-                for (int m = m0; m < m1; ++m) {
-                    const int id = ids[m], cnt = counts ? counts[m] : 1;
-                    const ChunkCode c = chunk_code(h, false, one, id);
-                    burst_fill_units(units.data() + unit_at[m], id, c.code, cnt, row_at[m], c.tp, h->dec_seq[id]);
-                    plan_burst_rows(*h->planners[id], c.T, c.kn, h->dec_seq[id], erasure + row_at[m], cnt,
-                                    flags.data() + row_at[m], coefs[p]);
-                    h->dec_seq[id] += cnt;
-                    for (int64_t ui = unit_at[m]; ui < unit_at[m + 1]; ++ui) {
-                        fec::BurstUnit& u = units[ui];
-                        u.coef = cbytes;
-                        for (int j = 0; j < u.cnt; ++j)
-                            if ((flags[u.row0 + j] & 3) == fec::kRecovered) cbytes += c.kn;
-                    }
+        DecodePlan<fec::BurstUnit> plan;
+        const bool ok = plan.plan(
+            h->pool.get(), counts, M, R, [&](int m) { return chunk_code(h, false, one, ids[m]).tp; },
+            [&](int m, int64_t row0, int cnt, fec::BurstUnit* u, uint8_t* fl, std::vector<uint8_t>& coefs) {
+                const int id = ids[m];
+                const ChunkCode c = chunk_code(h, false, one, id);
+                int64_t cbytes = static_cast<int64_t>(coefs.size());  // the part's coefficient bytes so far
+                fec::BurstUnit* end = burst_fill_units(u, id, c.code, cnt, row0, c.tp, h->dec_seq[id]);
+                plan_burst_rows(*h->planners[id], c.T, c.kn, h->dec_seq[id], erasure + row0, cnt, fl, coefs);
+                h->dec_seq[id] += cnt;
+                for (; u != end; ++u) {
+                    u->coef = cbytes;
+                    for (int j = 0; j < u->cnt; ++j)
+                        if ((fl[u->lead + j] & 3) == fec::kRecovered) cbytes += c.kn;
                 }
-            } catch (...) {
-                failed.store(true);
-            }
-        };
-        if (np > 1)
-            h->pool->run(part);
-        else
-            part(0);
-        if (failed.load()) return FEC_ERR_ARG;
-        // staging: units | row flags | coefficient blocks
-        const size_t off_flags = align16(static_cast<size_t>(nu) * sizeof(fec::BurstUnit));
-        const size_t off_coef = align16(off_flags + static_cast<size_t>(R));
-        size_t ncoef = 0;
-        for (const auto& c : coefs) ncoef += c.size();
-        const size_t bytes = off_coef + ncoef + 16;
-        if (int st = stage_reserve(h, b, bytes)) return st;
-        uint8_t* hs = static_cast<uint8_t*>(h->h_stage[b]);
-        size_t cbase = 0;
-        for (int p = 0; p < np; ++p) {  // a part's blocks follow those of the parts before it
-            const int m0 = static_cast<int>(static_cast<int64_t>(M) * p / np);
-            const int m1 = static_cast<int>(static_cast<int64_t>(M) * (p + 1) / np);
-            if (cbase)
-                for (int64_t ui = unit_at[m0]; ui < unit_at[m1]; ++ui) units[ui].coef += static_cast<int64_t>(cbase);
-            if (!coefs[p].empty()) std::memcpy(hs + off_coef + cbase, coefs[p].data(), coefs[p].size());
-            cbase += coefs[p].size();
-        }
-        std::memcpy(hs, units.data(), units.size() * sizeof(fec::BurstUnit));
-        std::memcpy(hs + off_flags, flags.data(), flags.size());
-        if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
-        const uint8_t* rec = static_cast<const uint8_t*>(h->upload ? h->d_stage[b] : h->m_stage[b]);
-        const fec::BurstDecRows rows{d_codeword, rec + off_flags, rec + off_coef, d_payload_out, d_payload_len};
+            },
+            [](fec::BurstUnit& u, int64_t by) { u.coef += by; });
+        if (!ok) return FEC_ERR_ARG;
+        if (int st = stage.reserve(plan.bytes)) return st;
+        plan.write(stage.host());
+        const uint8_t* rec = stage.device();
+        const fec::BurstDecRows rows{d_codeword, rec + plan.off_flags, rec + plan.off_coef, d_payload_out, d_payload_len};
         const fec::BurstUnit* du = reinterpret_cast<const fec::BurstUnit*>(rec);
         const dim3 grid(static_cast<unsigned>(nu));
         if (mixed) {
@@ -1200,12 +1014,7 @@ int decode_chunks(fec_streams* h, const int32_t* ids, const int32_t* counts, int
             a1.rows = rows, a1.units = du, a1.ring = h->d_ring, a1.g.gf = v.gf;
             hipLaunchKernelGGL(fec::fec_streams_decode_burst_kernel, grid, dim3(256), lds, s, a1);
         }
-        FS_TRY(hipGetLastError());
-        FS_TRY(hipEventRecord(h->done, s));
-        FS_TRY(hipEventRecord(h->staged[b], s));
-        h->buf = (b + 1) % fec_streams::kStageBufs;
-        poison.armed = false;
-        return FEC_OK;
+        return stage.commit(s);
     } catch (const std::bad_alloc&) {
         return FEC_ERR_NOMEM;
     } catch (...) {
@@ -1241,7 +1050,7 @@ int fec::stream_encode_one(const CodecView& v, uint8_t* win, const uint8_t* payl
     a.done = done;
     a.ticket = ticket;
     hipLaunchKernelGGL(fec::fec_streams_encode_kernel, dim3(1), dim3(256), 0, s, a);  // 256: the table loads
-    FS_TRY(hipGetLastError());
+    FEC_HIP(hipGetLastError());
     return FEC_OK;
 }
 
@@ -1266,7 +1075,7 @@ int fec::stream_decode_one(const CodecView& v, uint8_t* ring, const uint8_t* cw,
     a.done = done;
     a.ticket = ticket;
     hipLaunchKernelGGL(fec::fec_streams_decode_kernel, dim3(1), dim3(256), 0, s, a);  // 256: the table loads
-    FS_TRY(hipGetLastError());
+    FEC_HIP(hipGetLastError());
     return FEC_OK;
 }
 
@@ -1277,12 +1086,9 @@ int fec_streams_create(int max_payload, int T, int B, int N, int nstreams, fec_s
     *out = nullptr;
     try {
         std::unique_ptr<fec_streams> h(new fec_streams());
-        if (int st = fec_codec_create(max_payload, T, B, N, &h->codec)) return st;
-        fec::CodecView v;
-        if (int st = fec::codec_view(h->codec, &v)) return st;
-        h->g = fec::Geometry::make(max_payload, T, B, N);
+        if (!fec::stream_tuple(max_payload, T, B, N, &h->g)) return FEC_ERR_ARG;
         const fec::Geometry& g = h->g;
-        if (g.T + g.k > fec::kRR || g.k > 16 || g.k * g.n > 16 * 32) return FEC_ERR_ARG;
+        if (int st = fec_codec_create(max_payload, T, B, N, &h->codec)) return st;
         h->nstreams = nstreams;
         h->W = std::max(1, g.n - 1);
         h->SK = g.S * g.k;
@@ -1316,19 +1122,18 @@ int fec_streams_encode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
     if (!h->codes.empty())  // a mixed group: chunks of one packet
         return encode_chunks(h, ids, nullptr, M, 1, d_payload, d_payload_len, d_codeword, d_codeword_len,
                              static_cast<hipStream_t>(stream));
-    if (int st = check_ids(h, ids, M)) return st;
+    fec::GroupStage& stage = h->stage;
+    if (int st = stage.check_ids(ids, M)) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int b = 0;
-    if (int st = stage_free(h, s, &b)) return st;
-    int64_t* hseq = static_cast<int64_t*>(h->h_stage[b]);
+    if (int st = stage.begin(s)) return st;
+    fec::StageGuard guard{stage};
+    int64_t* hseq = reinterpret_cast<int64_t*>(stage.host());  // M seqs, M ids: within the buffers' size at create
     int32_t* hid = reinterpret_cast<int32_t*>(hseq + M);
     for (int m = 0; m < M; ++m) {
         hseq[m] = h->enc_seq[ids[m]];  // committed below, once the launch is in
         hid[m] = ids[m];
     }
-    const size_t bytes = static_cast<size_t>(M) * 12;
-    if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
-    const void* rec = h->upload ? h->d_stage[b] : h->m_stage[b];
+    const void* rec = stage.device();
     fec::CodecView v;
     fec::codec_view(h->codec, &v);
     fec::StreamsEncArgs a;
@@ -1354,10 +1159,7 @@ int fec_streams_encode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
     a.done = nullptr;
     a.ticket = 0;
     hipLaunchKernelGGL(fec::fec_streams_encode_kernel, dim3((M + 3) / 4), dim3(256), 0, s, a);
-    FS_TRY(hipGetLastError());
-    FS_TRY(hipEventRecord(h->done, s));
-    FS_TRY(hipEventRecord(h->staged[b], s));
-    h->buf = (b + 1) % fec_streams::kStageBufs;
+    if (int st = stage.commit(s)) return st;
     for (int m = 0; m < M; ++m) ++h->enc_seq[ids[m]];
     return FEC_OK;
 }
@@ -1372,23 +1174,14 @@ int fec_streams_decode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
     if (!h->codes.empty())  // a mixed group: chunks of one packet
         return decode_chunks(h, ids, nullptr, M, M, 1, erasure, d_codeword, d_payload_out, d_payload_len,
                              static_cast<hipStream_t>(stream));
-    static const bool dbg = std::getenv("FEC_STREAMS_DEBUG") != nullptr;  // per-phase host times
-    const auto t0 = std::chrono::steady_clock::now();
-    if (int st = check_ids(h, ids, M)) return st;
+    fec::GroupStage& stage = h->stage;
+    if (int st = stage.check_ids(ids, M)) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int b = 0;
-    const auto t1 = std::chrono::steady_clock::now();
-    if (int st = stage_free(h, s, &b)) return st;
-    const auto t2 = std::chrono::steady_clock::now();
+    if (int st = stage.begin(s)) return st;
+    fec::StageGuard guard{stage};  // the symbolic decoders advance below, before the launch
     const fec::Geometry& g = h->g;
-    // The symbolic decoders advance below, before the upload and the launch; if either fails, the
-    // host planners are ahead of the device rings and the group refuses every later call.
-    struct Poison {
-        fec_streams* h;
-        bool armed = true;
-        ~Poison() { if (armed) h->poisoned = true; }
-    } poison{h};
-    fec::StreamItem* items = static_cast<fec::StreamItem*>(h->h_stage[b]);
+    // M items and at most M coefficient blocks: within the buffers' size at create
+    fec::StreamItem* items = reinterpret_cast<fec::StreamItem*>(stage.host());
     uint8_t* coefs = reinterpret_cast<uint8_t*>(items + M);
     const int kn = g.k * g.n;
     std::atomic<int> ncoef_a{0};
@@ -1429,11 +1222,7 @@ int fec_streams_decode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
         steps(0, M);
     }
     if (failed.load()) return FEC_ERR_ARG;
-    const int ncoef = ncoef_a.load();
-    const auto t3 = std::chrono::steady_clock::now();
-    const size_t bytes = static_cast<size_t>(M) * sizeof(fec::StreamItem) + static_cast<size_t>(ncoef) * kn;
-    if (h->upload) FS_TRY(hipMemcpyAsync(h->d_stage[b], h->h_stage[b], bytes, hipMemcpyHostToDevice, s));
-    const void* rec = h->upload ? h->d_stage[b] : h->m_stage[b];
+    const void* rec = stage.device();
     fec::CodecView v;
     fec::codec_view(h->codec, &v);
     fec::StreamsDecArgs a;
@@ -1453,18 +1242,7 @@ int fec_streams_decode(fec_streams* h, const int32_t* ids, int M, const uint8_t*
     a.done = nullptr;
     a.ticket = 0;
     hipLaunchKernelGGL(fec::fec_streams_decode_kernel, dim3((M + 3) / 4), dim3(256), 0, s, a);
-    FS_TRY(hipGetLastError());
-    FS_TRY(hipEventRecord(h->done, s));
-    FS_TRY(hipEventRecord(h->staged[b], s));
-    h->buf = (b + 1) % fec_streams::kStageBufs;
-    poison.armed = false;
-    if (dbg) {
-        const auto t4 = std::chrono::steady_clock::now();
-        auto us = [](auto a, auto z) { return std::chrono::duration<double, std::micro>(z - a).count(); };
-        std::fprintf(stderr, "streams decode: ids %.1f us, stage wait %.1f, steps %.1f, upload + launch %.1f\n",
-                     us(t0, t1), us(t1, t2), us(t2, t3), us(t3, t4));
-    }
-    return FEC_OK;
+    return stage.commit(s);
 }
 
 int fec_streams_encode_burst(fec_streams* h, const int32_t* ids, const int32_t* counts, int M,
@@ -1594,10 +1372,10 @@ int fec_streams_create_mixed(int max_payload, const int32_t* tuples, int ncodes,
             dt[c].pad = 0;
             kn_max = std::max(kn_max, static_cast<size_t>(v.k) * v.n);
         }
-        FS_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_enc_codes), et.size() * sizeof(et[0])));
-        FS_TRY(hipMemcpy(h->d_enc_codes, et.data(), et.size() * sizeof(et[0]), hipMemcpyHostToDevice));
-        FS_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_dec_codes), dt.size() * sizeof(dt[0])));
-        FS_TRY(hipMemcpy(h->d_dec_codes, dt.data(), dt.size() * sizeof(dt[0]), hipMemcpyHostToDevice));
+        FEC_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_enc_codes), et.size() * sizeof(et[0])));
+        FEC_HIP(hipMemcpy(h->d_enc_codes, et.data(), et.size() * sizeof(et[0]), hipMemcpyHostToDevice));
+        FEC_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_dec_codes), dt.size() * sizeof(dt[0])));
+        FEC_HIP(hipMemcpy(h->d_dec_codes, dt.data(), dt.size() * sizeof(dt[0]), hipMemcpyHostToDevice));
         const size_t wb = static_cast<size_t>(nstreams) * h->win_slot;
         const size_t rb = static_cast<size_t>(nstreams) * fec::kRR * h->cw_stride;
         const size_t stage = static_cast<size_t>(nstreams) * (sizeof(fec::BurstUnit) + 1 + kn_max + 16) + 64;
@@ -1644,11 +1422,11 @@ int fec_streams_set_code(fec_streams* h, int id, int code) {
             // a one-code group's one-packet decode kernel reads the ring rows of packets before the
             // stream's start as the zero rows they were at create: zero them again, between the
             // last call and the next (both are ordered by `done`)
-            if (h->poisoned) return FEC_ERR_HIP;
+            if (h->stage.poisoned) return FEC_ERR_HIP;
             uint8_t* ring = h->d_ring + static_cast<size_t>(id) * fec::kRR * h->g.CW;
-            FS_TRY(hipStreamWaitEvent(nullptr, h->done, 0));
-            FS_TRY(hipMemsetAsync(ring, 0, static_cast<size_t>(fec::kRR) * h->g.CW, nullptr));
-            FS_TRY(hipEventRecord(h->done, nullptr));
+            FEC_HIP(hipStreamWaitEvent(nullptr, h->stage.done, 0));
+            FEC_HIP(hipMemsetAsync(ring, 0, static_cast<size_t>(fec::kRR) * h->g.CW, nullptr));
+            FEC_HIP(hipEventRecord(h->stage.done, nullptr));
         }
         h->planners[id] = std::move(pl);
         if (!h->codes.empty()) h->code_of[id] = code;

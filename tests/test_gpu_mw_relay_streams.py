@@ -320,6 +320,117 @@ def test_unaligned_buffers_and_strides(L):
             assert torch.equal(out.view(R, CW2)[sl], r_cw[a:b]), (s, a)
 
 
+def test_calls_alternating_between_two_hip_streams():
+    """12 calls of 3 flows in bursts of 1 to 5 packets, the even calls on one HIP stream and the odd ones on
+    another.  The caller's one event orders its hop-1 rows (written on the default stream) before both
+    streams; staging buffers, codeword rings and windows are the group's to order.  Every row, size and
+    fate equals the same calls on one stream, and the composition's."""
+    L, code1, code2, ns, calls = 64, (4, 2, 2), (3, 1, 1), 3, 12
+    (T1, B1, N1) = code1
+    counts_r = [np.array([1 + (r + 2 * s) % 5 for s in range(ns)], dtype=np.int32) for r in range(calls)]
+    ids_r = [np.roll(np.arange(ns, dtype=np.int32), r) for r in range(calls)]
+    total = [int(sum(c[list(i).index(s)] for c, i in zip(counts_r, ids_r))) for s in range(ns)]
+    rng = np.random.default_rng(71)
+    pats, cw1s, refs = [], [], []
+    for s in range(ns):
+        n = total[s]
+        pat = np.zeros(n, dtype=np.uint8)
+        pat[6 + s:6 + s + B1] = 1             # a burst the code recovers
+        pat[16 + s:16 + s + T1 + N1 + 2] = 1  # and one it cannot
+        cuts = np.array([c[list(i).index(s)] for c, i in zip(counts_r, ids_r)], dtype=np.int32)
+        fates = fec.plan_burst_host(L, T1, B1, N1, pat, cuts)
+        assert int((fates == 2).sum()) >= 1 and int((fates == 3).sum()) >= 1, s
+        lens = torch.from_numpy(rng.integers(0, L + 1, n).astype(np.int32)).cuda()
+        cw1, *ref = reference(L, code1, code2, fec.fill_payload(0, n, L, SEED + 70 + s), lens, pat)
+        assert np.array_equal(ref[2][T1:].cpu().numpy(), fates), s
+        pats.append(pat)
+        cw1s.append(cw1)
+        refs.append(ref)
+    # every call's rows, made up front on the default stream
+    sent = np.zeros(ns, dtype=np.int64)
+    er_r, rx_r = [], []
+    for ids, counts in zip(ids_r, counts_r):
+        er = np.concatenate([pats[s][sent[s]:sent[s] + c] for s, c in zip(ids, counts)])
+        rx_r.append(received(torch.cat([cw1s[s][sent[s]:sent[s] + c] for s, c in zip(ids, counts)]), er))
+        er_r.append(er)
+        sent[ids] += counts
+    assert list(sent) == total
+    ready = torch.cuda.Event()
+    ready.record()
+
+    def run(streams):
+        grp = MessageWiseRelayGroup(L, code1, code2, ns)
+        outs = []
+        for r in range(calls):
+            with torch.cuda.stream(streams[r % len(streams)]):
+                outs.append(grp.relay(ids_r[r], counts_r[r], er_r[r], rx_r[r]))
+        torch.cuda.synchronize()
+        return grp, outs
+
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    for st in (sa, sb):
+        st.wait_event(ready)
+    _, one = run([sa])
+    grp, two = run([sa, sb])
+    for a, b in zip(one, two):
+        for x, y in zip(a, b):
+            assert torch.equal(x, y)
+    sent[:] = 0
+    for r in range(calls):
+        row = 0
+        for s, c in zip(ids_r[r], counts_r[r]):
+            for x, ref in zip(two[r], refs[s]):
+                assert torch.equal(x[row:row + c], ref[sent[s]:sent[s] + c]), (r, s)
+            row += c
+            sent[s] += c
+    assert [grp.state(s) for s in range(ns)] == [(total[s], total[s] - T1) for s in range(ns)]
+
+
+def test_a_call_larger_than_the_groups_staging():
+    """2 flows x one burst of 600 packets with about 10 % erasures: 38 chunk records of 48 bytes, the row
+    flags and the coefficient blocks against staging buffers made for 2 flows (370 bytes), so the call
+    grows its buffer; then an ordinary call of 3 packets per flow through the next buffer of the ring.
+    Both equal StreamGroup(code1).decode_burst, lengths clipped to [0, L], then
+    StreamGroup(code2).encode_burst of the rows from the flows' first messages on."""
+    L, code1, code2 = 300, (10, 3, 3), (10, 3, 3)
+    T1, ns, n, more = code1[0], 2, 600, 3
+    k1, n1 = geometry(code1)
+    tp, _ = mw_relay_streams_fit(L, code1, code2)
+    assert ns * -(-n // tp) * 48 > ns * (48 + 1 + k1 * n1 + 16) + 64  # the records alone exceed a buffer at create
+    rng = np.random.default_rng(73)
+    ids = np.array([1, 0], dtype=np.int32)
+    pats = [(rng.random(n + more) < 0.1).astype(np.uint8) for _ in range(ns)]
+    for pat in pats:
+        fates = fec.plan_burst_host(L, *code1, pat, np.array([n, more], dtype=np.int32))
+        assert (fates == 2).any() and (fates == 3).any()
+    src, dec, enc = (fec.StreamGroup(L, *c, ns) for c in (code1, code1, code2))
+    grp = MessageWiseRelayGroup(L, code1, code2, ns)
+    fed = 0
+    for c in (n, more):
+        counts = np.full(ns, c, dtype=np.int32)
+        lens = torch.from_numpy(rng.integers(0, L + 1, ns * c).astype(np.int32)).cuda()
+        cw1, _ = src.encode_burst(ids, counts, fec.fill_payload(fed * ns, ns * c, L, SEED + 90), lens)
+        er = np.concatenate([pats[s][fed:fed + c] for s in ids])
+        rx = received(cw1, er)
+        cw2, wl, ft = grp.relay(ids, counts, er, rx)
+        msg, ml = dec.decode_burst(ids, counts, er, rx)
+        ml.clamp_(0, L)
+        lo = max(T1 - fed, 0)  # the flows' first messages are rows T1 - fed on of every burst
+        o, ol = enc.encode_burst(ids, np.full(ns, c - lo, dtype=np.int32), msg.view(ns, c, L)[:, lo:].reshape(-1, L),
+                                 ml.view(ns, c)[:, lo:].reshape(-1).contiguous())
+        torch.cuda.synchronize()
+        assert not cw2.view(ns, c, -1)[:, :lo].any() and not wl.view(ns, c)[:, :lo].any()
+        assert torch.equal(cw2.view(ns, c, -1)[:, lo:], o.view(ns, c - lo, -1))
+        assert torch.equal(wl.view(ns, c)[:, lo:], ol.view(ns, c - lo))
+        for j, s in enumerate(ids):
+            want = np.zeros(c, dtype=np.uint8)
+            f = fec.plan_burst_host(L, *code1, pats[s][:fed + c], np.array([fed, c] if fed else [c], dtype=np.int32))
+            want[lo:] = f[max(fed - T1, 0):]
+            assert np.array_equal(ft.view(ns, c)[j].cpu().numpy(), want), s
+        fed += c
+    assert [grp.state(s) for s in range(ns)] == [(n + more, n + more - T1)] * ns
+
+
 def test_argument_errors_leave_the_group_unchanged():
     L, (code1, code2) = 300, PAIRS[0]
     fl = flows(L, code1, code2)
