@@ -73,6 +73,12 @@ def lib() -> ctypes.CDLL:
     L.fec_encode_tile_fetch.argtypes = [i32, i32, i32, i32, i32, ip, ip, ip, ip]
     L.fec_codec_set_copy_path.argtypes = [vp, i32]
     L.fec_codec_set_plan_path.argtypes = [vp, i32]
+    L.fec_codec_set_recover_path.argtypes = [vp, i32]
+    L.fec_codec_set_recover_path.restype = i32
+    L.fec_recover_fast_items.argtypes = [i32, i32, i32, i32, i64, i64, vp, vp, vp]
+    L.fec_recover_fast_items.restype = i32
+    L.fec_recover_fast_mul.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+    L.fec_recover_fast_mul.restype = ctypes.c_uint32
     L.fec_codec_info.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
     L.fec_codec_set_episode_dedup.argtypes = [vp, i32]
     L.fec_debug_stamps.argtypes = [vp, i32, vp]

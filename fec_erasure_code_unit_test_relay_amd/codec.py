@@ -94,11 +94,17 @@ class Codec:
         code = {"auto": 0, "generic": 1, "fast": 2}[path]
         check(lib().fec_codec_set_copy_path(self._h, code), "fec_codec_set_copy_path")
 
+    def set_recover_path(self, path: str) -> None:
+        """'auto', 'generic' (fec_recover_kernel_t) or 'fast' (the (k, n-k)-specialised kernel of
+        packed GF(2^8) products, auto's choice when it applies) for the decoder's recovery kernel."""
+        code = {"auto": 0, "generic": 1, "fast": 2}[path]
+        check(lib().fec_codec_set_recover_path(self._h, code), "fec_codec_set_recover_path")
+
     def info(self) -> dict:
         """Kernel configuration chosen for this codec on this device."""
         import json
-        buf = ctypes.create_string_buffer(512)
-        check(lib().fec_codec_info(self._h, buf, 512), "fec_codec_info")
+        buf = ctypes.create_string_buffer(1024)
+        check(lib().fec_codec_info(self._h, buf, 1024), "fec_codec_info")
         return json.loads(buf.value.decode())
 
     def set_plan_path(self, path: str) -> None:

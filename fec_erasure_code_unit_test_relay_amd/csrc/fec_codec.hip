@@ -17,6 +17,7 @@
 #include "fec_amd.h"
 #include "fec_host.h"
 #include "fec_kernels.h"
+#include "fec_recover_fast.h"
 #include "fec_status.h"
 
 using fec::Geometry;
@@ -69,6 +70,7 @@ struct fec_codec {
     int copyf_tp = 0;
     int copy_path = 0;           // 0 auto, 1 generic, 2 specialised (LDS tiles)
     int plan_path = 0;
+    int recover_path = 0;        // 0 auto, 1 generic, 2 specialised (packed products)
     int dedup = 1;               // episode-shape deduplication in the planner
     uint64_t* d_stamps = nullptr;  // diagnostics: phase stamps of the next specialised launch
     int stamp_kernel = -1;
@@ -563,6 +565,15 @@ int launch_compact(fec_codec* c, int64_t P, void* d_ws, size_t ws_bytes, hipStre
     return FEC_OK;
 }
 
+// The (k, n-k)-specialised recovery kernel of a geometry, or null (no instance for the pair, or the
+// span of rows a packet touches exceeds the staging limit: long codewords such as L = 1500, or k = 1,
+// 2 at L = 300): the one test launch_recover, fec_codec_set_recover_path, fec_codec_info and the
+// host-only fec_recover_fast_items use.  The kernel takes any alignment of the buffers and any L.
+const void* recover_fast_kernel(const Geometry& g) {
+    if (fec::rec_fast_span_max(g.k, g.n, g.CW) > fec::kRecFastStageMax) return nullptr;
+    return fec::fec_recover_fast_kernel_for(g.k, g.n - g.k);
+}
+
 // Byte half of the erased packets: one wave per recovered packet of rec_list.  `compacted`: the
 // list was built on this stream's side already (launch_decode); otherwise it is built here first.
 int launch_recover(fec_codec* c, const uint8_t* d_cw, int64_t P, uint8_t* d_out, int32_t* d_outlen,
@@ -593,6 +604,18 @@ int launch_recover(fec_codec* c, const uint8_t* d_cw, int64_t P, uint8_t* d_out,
     if (int st = c->begin(FEC_KERNEL_DEC_RECOVER, s, &stop)) return st;
     ra.row_off = row_off;
     ra.stamps = (c->stamp_kernel == FEC_KERNEL_DEC_RECOVER) ? c->d_stamps : nullptr;
+    if (c->recover_path != 0 && c->recover_path != 1 && c->recover_path != 2) return FEC_ERR_ARG;
+    const void* fk = recover_fast_kernel(g);
+    if (c->recover_path == 2 && !fk) return FEC_ERR_ARG;
+    if (fk && c->recover_path != 1) {
+        // one wave (= one workgroup) per kRecFastWaveRows output rows, at most kRecFastMaxWaves:
+        // a wave walks r += waves when more packets than that are recovered
+        ra.stage_bytes = round16(fec::rec_fast_span_max(g.k, g.n, g.CW));
+        void* args[] = {&ra};
+        HIP_TRY(hipLaunchKernel(fk, dim3(static_cast<unsigned>(fec::rec_fast_waves(Pout))), dim3(64), args,
+                                fec::recover_fast_lds_bytes(g.k, g.n, ra.stage_bytes, g.L), s));
+        return c->end(stop, s);
+    }
     // the k+n-1 rows a recovered packet reads, staged in LDS when they fit 12 KB per wave
     // (fec_recover_kernel_t's kRecStageChunks)
     const int span = (g.k + g.n - 1) * g.CW + 32;
@@ -1001,12 +1024,22 @@ int fec_codec_info(const fec_codec* c, char* buf, size_t size) {
         std::snprintf(cpy, sizeof(cpy), "fec_copy_fast_kernel<%d, %d>", c->g.k, np);
     else
         std::snprintf(cpy, sizeof(cpy), "fec_copy_kernel");
+    // the recovery: its kernel, and its launch's waves = min(recover_waves, ceil(output rows /
+    // recover_wave_rows)) (the generic kernel: 4 waves per workgroup, a wave per row)
+    char rec[64];
+    const bool rfast = c->recover_path != 1 && recover_fast_kernel(c->g);
+    if (rfast)
+        std::snprintf(rec, sizeof(rec), "fec_recover_fast_kernel<%d, %d>", c->g.k, np);
+    else
+        std::snprintf(rec, sizeof(rec), "fec_recover_kernel_t<%d, %s>", c->g.n <= 17 ? 17 : 32,
+                      c->g.n <= 17 && (c->g.k + c->g.n - 1) * c->g.CW + 32 <= 12 * 1024 ? "true" : "false");
     std::snprintf(buf, size,
                   "{\"k\": %d, \"n\": %d, \"S\": %d, \"CW\": %d, \"encode_kernel\": \"%s\", "
                   "\"copy_kernel\": \"%s\", \"encode_tile_packets\": %d, \"encode_tile_workgroups_per_cu\": %d, "
-                  "\"copy_tile\": %d, \"plan_specialised\": %d}",
+                  "\"copy_tile\": %d, \"plan_specialised\": %d, \"recover_kernel\": \"%s\", "
+                  "\"recover_waves\": %d, \"recover_wave_rows\": %d}",
                   c->g.k, c->g.n, c->g.S, c->g.CW, enc, cpy, c->tile.R, c->tile_per_cu, c->copyf_tp,
-                  c->plan_fast ? 1 : 0);
+                  c->plan_fast ? 1 : 0, rec, rfast ? fec::kRecFastMaxWaves : 4096, rfast ? fec::kRecFastWaveRows : 1);
     return FEC_OK;
 }
 
@@ -1045,6 +1078,52 @@ int fec_codec_set_copy_path(fec_codec* c, int path) {
     if (path == 2 && !c->copy_fast) return FEC_ERR_ARG;
     c->copy_path = path;
     return FEC_OK;
+}
+
+int fec_codec_set_recover_path(fec_codec* c, int path) {
+    if (!c || path < 0 || path > 2) return FEC_ERR_ARG;
+    if (path == 2 && !recover_fast_kernel(c->g)) return FEC_ERR_ARG;
+    c->recover_path = path;
+    return FEC_OK;
+}
+
+int fec_recover_fast_items(int max_payload, int T, int B, int N, int64_t P, int64_t x, int64_t* span,
+                           int64_t* src_off, int32_t* out_idx) {
+    if (max_payload < 1 || T < 0 || B < 0 || N < 1 || N > T || B < N || P < 0) return FEC_ERR_ARG;
+    if (T - N + 1 > fec::kMaxK || T - N + 1 + B > fec::kMaxN - 1) return 0;  // no codec of this geometry
+    const Geometry g = Geometry::make(max_payload, T, B, N);
+    if (!recover_fast_kernel(g)) return 0;
+    const int items = g.k * ((g.S + 3) / 4);
+    if (!span) return items;
+    if (x < 0 || x >= P - T) return FEC_ERR_ARG;
+    const fec::RecFastSpan sp = fec::rec_fast_span(x, g.k, g.n, g.CW, P);
+    span[0] = sp.rlo;
+    span[1] = sp.rhi;
+    span[2] = sp.a0;  // the staged bytes: 16-byte pieces from a0, cut at the buffer's end
+    span[3] = std::min<int64_t>(sp.a0 + 16 * static_cast<int64_t>(sp.nb), P * g.CW);
+    span[4] = round16(fec::rec_fast_span_max(g.k, g.n, g.CW));  // LDS bytes they may take
+    if (!src_off || !out_idx) return items;
+    for (int it = 0; it < items; ++it) {
+        const fec::RecFastItem m = fec::rec_fast_item(sp, x, it, g.k, g.n, g.S, g.CW, P);
+        for (int q = 0; q < g.n; ++q)
+            for (int e = 0; e < 4; ++e) {
+                const bool use = q >= m.qlo && q < m.qhi && e < m.ne;
+                // staged offset -> byte of the codeword buffer (the kernel reads the staged copy)
+                src_off[(static_cast<int64_t>(it) * g.n + q) * 4 + e] =
+                    use ? sp.a0 + m.base + q * (g.CW + 1) + e * g.n : -1;
+            }
+        for (int e = 0; e < 4; ++e) {
+            const int h = (4 * m.g + e) * g.k + m.i;
+            out_idx[it * 4 + e] = (e < m.ne && h < g.L + 2) ? h : -1;
+        }
+    }
+    return items;
+}
+
+uint32_t fec_recover_fast_mul(uint32_t c, uint32_t x4) {
+    uint32_t tab[5];
+    fec::gf_mul4x_tables(c, tab);
+    return fec::gf_mul4x_portable(tab, x4);
 }
 
 int fec_codec_set_encode_path(fec_codec* c, int path) {

@@ -179,10 +179,6 @@ __global__ __launch_bounds__(256) void fec_copy_pair_kernel(CopyFastArgs a) {
     copy_tile_convert<K, NP>(a, xb, nb, db, raw, xo, clen, erw);
 }
 
-#define FEC_COPY_FAST_LIST(X) \
-    X(8, 3) X(9, 5) X(11, 0) X(10, 1) X(9, 2) X(7, 4) X(6, 5) X(5, 6) X(4, 7) X(3, 8) X(2, 9)  \
-    X(1, 10) X(10, 3) X(9, 3) X(10, 4) X(8, 4) X(10, 5) X(7, 5) X(3, 9)
-
 #define FEC_COPY_FAST_INST(K, NP) \
     template __global__ void fec_copy_fast_kernel<K, NP>(CopyFastArgs); \
     template __global__ void fec_copy_pair_kernel<K, NP>(CopyFastArgs);

@@ -185,6 +185,12 @@ struct CopyFastArgs {
     uint64_t* stamps;           // diagnostics: per-workgroup phase timestamps (null = off)
 };
 
+// The (k, n-k) pairs the specialised decode kernels (copy: fec_copy_fast.hip, recovery:
+// fec_recover_fast.hip) are instantiated for.
+#define FEC_COPY_FAST_LIST(X) \
+    X(8, 3) X(9, 5) X(11, 0) X(10, 1) X(9, 2) X(7, 4) X(6, 5) X(5, 6) X(4, 7) X(3, 8) X(2, 9)  \
+    X(1, 10) X(10, 3) X(9, 3) X(10, 4) X(8, 4) X(10, 5) X(7, 5) X(3, 9)
+
 // fec_copy_fast_kernel<k, n-k> for the instantiated pairs (fec_copy_fast.hip), else nullptr.
 const void* fec_copy_fast_kernel_for(int k, int np);
 constexpr int kPairQ = 6;  // 16-byte chunks per thread a tile's stage may take (6 * 16 * 256 = 24 KB)
@@ -287,6 +293,13 @@ inline int recover_lds_bytes(int maxn, int stage_bytes) {
 }
 template <int MAXN, bool STAGED>
 __global__ void fec_recover_kernel_t(RecArgs a);
+// fec_recover_fast_kernel<k, n-k> for the instantiated pairs (fec_recover_fast.hip), else nullptr:
+// one wave per workgroup, dynamic LDS recover_fast_lds_bytes (packed tables + staged span + row),
+// RecArgs::stage_bytes = the span rounded up to 16 (at most kRecFastStageMax, fec_recover_fast.h).
+const void* fec_recover_fast_kernel_for(int k, int np);
+inline int recover_fast_lds_bytes(int k, int n, int stage_bytes, int L) {
+    return ((20 * k * n + 15) & ~15) + stage_bytes + ((L + 16 + 15) & ~15);
+}
 
 
 // Block mode (fec_block.hip): many independent code blocks of n symbols.

@@ -80,6 +80,26 @@ int fec_encode_tile_fetch(int max_payload, int T, int B, int N, int seg, int *R,
  * one), 1 generic, 2 LDS-tile specialised.  Ids 3-6 (barrier-free wave, persistent tile, chunk and
  * per-wave LDS-DMA pipeline copies, all measured slower in the step) are retired. */
 int fec_codec_set_copy_path(fec_codec *codec, int path);
+/* The same switch for the decoder's recovery kernel: 0 automatic (the (k, n-k)-specialised kernel
+ * of packed GF(2^8) products when one is compiled for the pair and the k+n-1 codeword rows a packet
+ * touches fit its 12 KB staging limit, for any max_payload and any alignment of the buffers; else
+ * the generic one), 1 generic, 2 specialised (FEC_ERR_ARG where it does not apply).  fec_codec_info
+ * names the kernel ("recover_kernel") and gives its launch's wave count: min(recover_waves,
+ * ceil(output rows / recover_wave_rows)). */
+int fec_codec_set_recover_path(fec_codec *codec, int path);
+/* Host-only (no device call): the index arithmetic of the specialised recovery kernel, through the
+ * functions the kernel itself uses (fec_recover_fast.h).  Returns its work items per packet,
+ * k * ceil(S / 4), for (max_payload, T, B, N), or 0 when the kernel does not apply (outputs
+ * untouched); FEC_ERR_ARG for a refused tuple or x outside [0, P - T).  With span != NULL, for
+ * packet x of a P-packet buffer: span[0..1] = first and one-past-last codeword row of the
+ * diagonals inside [0, P), span[2..3] = the byte range of the codeword buffer the wave loads,
+ * span[4] = the LDS bytes set aside for it.  With src_off and out_idx too: src_off[(item * n + q)
+ * * 4 + e] = byte of the codeword buffer that term q of the item's sub-stream e reads (-1: absent),
+ * out_idx[item * 4 + e] = the byte of [len_hi, len_lo, payload] it produces (-1: none). */
+int fec_recover_fast_items(int max_payload, int T, int B, int N, int64_t P, int64_t x, int64_t *span,
+                           int64_t *src_off, int32_t *out_idx);
+/* Host-only: c * (each byte of x4) in GF(2^8), through the kernel's packed-doubling table builder. */
+uint32_t fec_recover_fast_mul(uint32_t c, uint32_t x4);
 /* The same switch for the decoder's planner (per-episode block replay). */
 int fec_codec_set_plan_path(fec_codec *codec, int path);
 /* Planner: replay one episode per distinct loss shape and copy its results to the other episodes
