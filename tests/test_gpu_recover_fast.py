@@ -8,7 +8,11 @@ kernel); every case also asserts, from the oracle alone, that its pattern recove
 
 The packed product is checked for all 65 536 pairs on the CPU (tests/test_recover_fast_host.py: the
 table builder is host-callable), so no crafted stream is needed for it here.  No decode test of
-this suite runs under graph capture, so there is none here either."""
+this suite runs under graph capture, so there is none here either.
+
+The cases of this file stay around four (k, n-k) pairs; tests/test_gpu_recover_fast_pairs.py runs
+every instance of FEC_COPY_FAST_LIST through the helpers and case bodies defined here (RECOVERED
+and NO_EDGE_ROWS hold the oracle's figures for every code of that sweep)."""
 import functools
 
 import numpy as np
@@ -29,7 +33,14 @@ FAST_SIZES = [(300, (10, 3, 3)), (300, (10, 5, 2)), (300, (10, 1, 1)), (64, (10,
               (301, (10, 3, 3)), (299, (10, 4, 3))]
 GENERIC_SIZES = [(300, (10, 10, 10)), (300, (10, 9, 1))]  # long codewords; n = 19 (tests/test_gpu_parity.py DEC_CASES)
 # recovered packets of the base pattern on the CPU oracle, per (T, B, N)
-RECOVERED = {(10, 3, 3): 43, (10, 5, 2): 43, (10, 4, 3): 43, (10, 1, 1): 37, (10, 10, 10): 57, (10, 9, 1): 44}
+RECOVERED = {(10, 3, 3): 43, (10, 5, 2): 43, (10, 4, 3): 43, (10, 1, 1): 37, (10, 10, 10): 57, (10, 9, 1): 44,
+             # the other codes of FEC_COPY_FAST_LIST: the same count at L = 1, 300, the largest L
+             # the specialised kernel takes and that L + 1
+             (10, 2, 2): 37, (10, 4, 4): 47, (10, 5, 5): 47, (10, 6, 6): 49, (10, 7, 7): 51, (10, 8, 8): 53,
+             (10, 9, 9): 55, (10, 3, 1): 38, (10, 3, 2): 41, (10, 4, 1): 42, (10, 5, 1): 42, (10, 5, 4): 47,
+             (10, 9, 8): 54, (10, 0, 0): 0}
+# codes whose oracle does not recover all of rows 0, 1, 3, P-3 and P-1 of the base pattern
+NO_EDGE_ROWS = {(10, 1, 1), (10, 2, 2), (10, 3, 1), (10, 3, 2), (10, 4, 1), (10, 5, 1), (10, 0, 0)}
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -65,7 +76,7 @@ def base_stream(L, tbn):
     rec = recovered_rows(pat, ref["out_len"])
     assert int(pat[:P_BASE].sum()) == 77
     assert int(rec.sum()) >= RECOVERED[tbn], (L, tbn, int(rec.sum()))
-    if tbn != (10, 1, 1):
+    if tbn not in NO_EDGE_ROWS:
         assert rec[[0, 1, 3, P_BASE - 3, P_BASE - 1]].all()
     return pat, ref
 
@@ -111,6 +122,11 @@ def test_fast_sizes(L, tbn):
 
 @pytest.mark.parametrize("L,tbn", GENERIC_SIZES)
 def test_generic_sizes_refuse_fast(L, tbn):
+    refuse_fast_case(L, tbn)
+
+
+def refuse_fast_case(L, tbn):
+    """A size the specialised kernel does not take: "fast" refused, "auto" and "generic" the oracle's."""
     pat, ref = base_stream(L, tbn)
     c = fec.Codec(L, *tbn)
     assert not fast_applies(c)
@@ -128,8 +144,20 @@ def test_generic_sizes_refuse_fast(L, tbn):
 
 @pytest.mark.parametrize("L,tbn", [(300, (10, 3, 3)), (301, (10, 3, 3)), (64, (10, 5, 2))])
 def test_variable_lengths(L, tbn):
+    variable_lengths_case(L, tbn)
+
+
+def variable_lengths_case(L, tbn):
     """Recovered rows of length 0, of length L and in between: zero tail and length word, against the
     oracle's per-packet coders."""
+    pat, cws, want, want_len = variable_lengths_ref(L, tbn)
+    c = fec.Codec(L, *tbn)
+    cw, er = place(garbled(cws, pat, L)), place(pat)
+    decode_both(c, cw, er, want, want_len, P_BASE)
+
+
+def variable_lengths_ref(L, tbn):
+    """The oracle's half of variable_lengths_case (no device): pattern, codewords, rows, lengths."""
     T, B, N = tbn
     rows = P_BASE + T
     pat = base_pattern(P_BASE, T)
@@ -151,25 +179,27 @@ def test_variable_lengths(L, tbn):
     # (a recovered row of length 0 reads as lost here)
     assert int(rec.sum()) >= RECOVERED[tbn] - int(((pat[:P_BASE] == 1) & (lens[:P_BASE] == 0)).sum())
     assert want_len[0] == L and want_len[3] == L // 3 and want_len[40] == 1 and (want[1] == 0).all()
-    c = fec.Codec(L, T, B, N)
-    cw, er = place(garbled(np.stack(cws), pat, L)), place(pat)
-    decode_both(c, cw, er, want, want_len, P_BASE)
+    return pat, np.stack(cws), want, want_len
 
 
 def test_tiny_batches():
     """1, 2, k, n and n + 1 output rows, packet 0 erased: what is recovered is the oracle's to say."""
-    L, tbn = 300, (10, 3, 3)
+    assert any(tiny_batches_case(300, (10, 3, 3))), "no size recovers row 0"
+
+
+def tiny_batches_case(L, tbn):
+    """The loop of test_tiny_batches; per size, whether the oracle recovers row 0."""
     T = tbn[0]
     c = fec.Codec(L, *tbn)
     row0 = []
-    for P in (1, 2, c.k, c.n, c.n + 1):
+    for P in dict.fromkeys((1, 2, c.k, c.n, c.n + 1)):
         pat = np.zeros(P + T, dtype=np.uint8)
         pat[0] = 1
         ref = oracle.run_stream(L, *tbn, P, pat, seed=SEED + P, want_data=True, want_codewords=True)
         row0.append(bool(ref["out_len"][0] > 0))
         cw, er = place(garbled(ref["cw"], pat, P)), place(pat)
         decode_both(c, cw, er, ref["out_data"], ref["out_len"], P)
-    assert any(row0), "no size recovers row 0"
+    return row0
 
 
 @pytest.mark.parametrize("cw_off,out_off", [(1, 0), (2, 0), (3, 0), (0, 1), (0, 2), (0, 3), (1, 1), (2, 2), (3, 3)])

@@ -2,8 +2,17 @@
 fec_recover_fast_items / fec_recover_fast_mul): which geometries take it, that every source byte it
 reads lies inside the codeword buffer, that every byte of [len_hi, len_lo, payload] is produced
 exactly once, and all 65 536 products of the packed-doubling tables.  The kernel computes its
-spans, item offsets and tables through the same functions.  No device work here."""
+spans, item offsets and tables through the same functions.  No device work here.
+
+The sweep covers every instance: the (k, n-k) pairs are read from FEC_COPY_FAST_LIST in
+csrc/fec_kernels.h (19 of them; a new instance extends the sweep or fails it), the predicate is
+compared with (k+n-1) * n * ceil((L+2)/k) + 32 <= 12 288 for every L up to 2000, the largest
+payload size each pair accepts (LMAX) is derived from that formula, and the bounds and coverage are
+checked for every pair at L = 1, 2, 300 (where it applies) and LMAX.  tests/test_gpu_recover_fast.py
+takes the pairs and LMAX from here."""
 import ctypes
+import os
+import re
 
 import numpy as np
 import pytest
@@ -12,7 +21,10 @@ import oracle
 
 import fec_erasure_code_unit_test_relay_amd as fec
 
-# (max_payload, (T, B, N)): the seven sizes of tests/test_gpu_recover_fast.py and (10,10,10)
+STAGE_MAX = 12 * 1024  # kRecFastStageMax (fec_recover_fast.h)
+
+# (max_payload, (T, B, N)): the seven sizes of tests/test_gpu_recover_fast.py and (10,10,10);
+# every_pair_sizes() below adds each instance's
 SIZES = [(300, (10, 3, 3)), (300, (10, 5, 2)), (300, (10, 1, 1)), (64, (10, 5, 2)), (2, (10, 3, 3)),
          (301, (10, 3, 3)), (299, (10, 4, 3)), (300, (10, 10, 10))]
 
@@ -36,6 +48,55 @@ APPLIES = {
     (37, (10, 9, 8)): 3 * 4,      # k 3, n 12, S 13, CW 156
 }
 
+# Largest max_payload at which fec_recover_fast_kernel<k, n-k> applies, per (k, n-k): the staged span
+# (k+n-1) * n * ceil((L+2)/k) + 32 is then the closest to the 12 288-byte limit.  Derived again from
+# the formula in test_predicate_equals_formula.
+LMAX = {(8, 3): 486, (9, 5): 349, (10, 1): 548, (9, 2): 520, (7, 4): 453, (6, 5): 412, (5, 6): 368,
+        (4, 7): 314, (3, 8): 253, (2, 9): 182, (1, 10): 99, (10, 3): 418, (9, 3): 457, (10, 4): 378,
+        (8, 4): 422, (10, 5): 338, (7, 5): 390, (3, 9): 214}
+
+
+def fast_pairs():
+    """The (k, n-k) pairs of FEC_COPY_FAST_LIST, in the header's order."""
+    path = os.path.join(os.path.dirname(os.path.abspath(fec.__file__)), "csrc", "fec_kernels.h")
+    with open(path) as f:
+        text = f.read()
+    body = re.search(r"#define\s+FEC_COPY_FAST_LIST\(X\)((?:[^\n]*\\\n)*[^\n]*)", text).group(1)
+    return [(int(k), int(np_)) for k, np_ in re.findall(r"\bX\(\s*(\d+)\s*,\s*(\d+)\s*\)", body)]
+
+
+PAIRS = fast_pairs()
+REC_PAIRS = [p for p in PAIRS if p[1] > 0]  # (11, 0) recovers nothing
+
+
+def tbn_of(pair):
+    """(k, n-k) -> (T, B, N) at T = 10: k = T - N + 1, n = k + B."""
+    k, np_ = pair
+    return (10, np_, 11 - k)
+
+
+def span_formula(k, n, L):
+    """Bytes of the widest staged span: k+n-1 codeword rows of n * ceil((L+2)/k) bytes, + 32."""
+    return (k + n - 1) * n * (-(-(L + 2) // k)) + 32
+
+
+def every_pair_sizes():
+    """Each instance at L = 1, 2, 300 (where it applies) and its LMAX, with the work items per packet
+    k * ceil(S / 4) computed here for the sizes APPLIES does not list."""
+    sizes = []
+    for k, np_ in REC_PAIRS:
+        lmax = LMAX[(k, np_)]
+        for L in sorted({1, 2, lmax} | ({300} if lmax >= 300 else set())):
+            key = (L, tbn_of((k, np_)))
+            S = -(-(L + 2) // k)
+            APPLIES.setdefault(key, k * (-(-S // 4)))
+            if key not in SIZES and key not in sizes:
+                sizes.append(key)
+    return sizes
+
+
+SIZES = SIZES + every_pair_sizes()
+
 
 def items(L, tbn, P=0, x=0, span=None, src=None, out=None):
     vp = ctypes.c_void_p
@@ -49,6 +110,47 @@ def test_predicate_table():
         assert items(L, tbn) == want, (L, tbn)
     assert items(300, (10, 1, 3)) == -1  # B < N
     assert set(SIZES) <= set(APPLIES)
+
+
+def test_pair_list():
+    """19 distinct instances; each maps to a code (10, B, N) with B >= N, but for (11, 0)."""
+    assert len(PAIRS) == 19 and len(set(PAIRS)) == 19, PAIRS
+    assert set(REC_PAIRS) == set(LMAX) and len(REC_PAIRS) == 18
+    assert set(PAIRS) - set(REC_PAIRS) == {(11, 0)}
+    for pair in PAIRS:
+        k, np_ = pair
+        T, B, N = tbn_of(pair)
+        assert (T - N + 1, T - N + 1 + B) == (k, k + np_) and 0 <= N <= T
+        assert B >= N or pair == (11, 0), pair
+    assert tbn_of((11, 0)) == (10, 0, 0)
+    assert items(300, (10, 0, 0)) == -1  # N = 0: nothing to recover, rejected
+    # the sweep of test_bounds_and_coverage holds every instance at its smallest and largest size
+    for pair in REC_PAIRS:
+        assert {(1, tbn_of(pair)), (LMAX[pair], tbn_of(pair))} <= set(SIZES), pair
+
+
+@pytest.mark.parametrize("pair", REC_PAIRS, ids=lambda p: "k%d-np%d" % p)
+def test_predicate_equals_formula(pair):
+    """fec_recover_fast_items > 0 exactly where the span formula fits the staging limit, for every
+    L in 1 .. 2000; the largest such L is the table's LMAX and its item count k * ceil(S / 4)."""
+    k, np_ = pair
+    n = k + np_
+    tbn = tbn_of(pair)
+    fits = []
+    for L in range(1, 2001):
+        want = span_formula(k, n, L) <= STAGE_MAX
+        got = items(L, tbn)
+        assert (got > 0) == want, (pair, L, got)
+        if want:
+            S = -(-(L + 2) // k)
+            assert got == k * (-(-S // 4)), (pair, L, got)
+            fits.append(L)
+        else:
+            assert got == 0, (pair, L, got)
+    lmax = max(fits)
+    assert fits == list(range(1, lmax + 1))  # the span grows with L
+    assert lmax == LMAX[pair], (pair, lmax)
+    assert span_formula(k, n, lmax) <= STAGE_MAX < span_formula(k, n, lmax + 1)
 
 
 @pytest.mark.parametrize("L,tbn", SIZES)
