@@ -167,6 +167,11 @@ def lib() -> ctypes.CDLL:
     L.fec_mw_relay_streams_relay.argtypes = [vp, vp, vp, i32, vp, vp, i64, vp, vp, vp, vp]
     L.fec_mw_relay_streams_state.argtypes = [vp, i32, i64p, i64p]
     L.fec_mw_relay_streams_fit.argtypes = [i32, i32, i32, i32, i32, i32, i32, ip, ip]
+    L.fec_mw_relay_streams_create_mixed.argtypes = [i32, vp, i32, vp, i32, ctypes.POINTER(vp)]
+    L.fec_mw_relay_streams_codes.argtypes = [vp, ip, ip, ip]
+    L.fec_mw_relay_streams_stream_geometry.argtypes = [vp, i32, ip, ip, ip, ip, ip, ip, ip, ip]
+    L.fec_mw_relay_streams_set_code.argtypes = [vp, i32, i32]
+    L.fec_mw_relay_streams_mixed_fit.argtypes = [i32, vp, i32, vp, vp]
     L.fec_sdswdf_create.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
     L.fec_sdswdf_destroy.argtypes = [vp]
     L.fec_sdswdf_geometry.argtypes = [vp, ip, ip, ip, ip, ip, ip, ip]
@@ -202,7 +207,10 @@ def lib() -> ctypes.CDLL:
                  "fec_relay_streams_create_mixed", "fec_relay_streams_codes", "fec_relay_streams_stream_geometry",
                  "fec_relay_streams_set_code", "fec_relay_streams_mixed_fit",
                  "fec_mw_relay_streams_create", "fec_mw_relay_streams_destroy", "fec_mw_relay_streams_geometry",
-                 "fec_mw_relay_streams_relay", "fec_mw_relay_streams_state", "fec_mw_relay_streams_fit", "fec_codec_create", "fec_codec_destroy", "fec_codec_set_encode_path",
+                 "fec_mw_relay_streams_relay", "fec_mw_relay_streams_state", "fec_mw_relay_streams_fit",
+                 "fec_mw_relay_streams_create_mixed", "fec_mw_relay_streams_codes",
+                 "fec_mw_relay_streams_stream_geometry", "fec_mw_relay_streams_set_code",
+                 "fec_mw_relay_streams_mixed_fit", "fec_codec_create", "fec_codec_destroy", "fec_codec_set_encode_path",
                  "fec_encode_tile_fetch", "fec_codec_set_copy_path", "fec_codec_set_plan_path", "fec_codec_info", "fec_codec_set_episode_dedup", "fec_debug_stamps", "fec_codec_geometry",
                  "fec_codec_generator", "fec_encode_batch", "fec_decode_batch", "fec_decode_plan",
                  "fec_decode_stream_create", "fec_decode_stream_destroy", "fec_decode_stream_state",

@@ -278,6 +278,8 @@ class MessageWiseRelayGroup:
     re-encodes them in one launch; per flow the rows of all calls together are
     StreamGroup(code1).decode_burst over the flow's hop-1 sequence, the first T1 rows dropped, then
     StreamGroup(code2).encode_burst.  The destination is StreamGroup(max_payload, *code2).decode_burst.
+    ``mixed`` makes a group whose flows each run their own pair of codes and may change it (``set_code``);
+    ``codes`` lists the group's pairs and ``code_of`` every flow's pair index (one pair and zeros here).
     This is not the reference's adaptive message-wise session (relay headers, acknowledgements)."""
 
     def __init__(self, max_payload: int, code1, code2, nstreams: int):
@@ -291,6 +293,54 @@ class MessageWiseRelayGroup:
         self.cw1_bytes, self.cw2_bytes, self.delay = (x.value for x in v)
         self.L, self.nstreams = max_payload, nstreams
         self.code1, self.code2 = (T1, B1, N1), (T2, B2, N2)
+        self.codes = [(self.code1, self.code2)]
+        self.code_of = [0] * nstreams
+
+    @classmethod
+    def mixed(cls, max_payload: int, pairs, code_of) -> "MessageWiseRelayGroup":
+        """A group whose flow s runs pair pairs[code_of[s]] = ((T1, B1, N1), (T2, B2, N2)), or a row
+        of an [ncodes, 6] array (fec_mw_relay_streams_create_mixed): one call serves flows of different
+        pairs in one launch.  Every row array has one stride for the group: ``cw1_bytes`` (the least
+        codeword row) and ``cw2_bytes`` are the largest of the pairs'; a flow's hop-1 codeword or hop-2
+        codeword is the first geometry(s)[...] bytes of its row, and the rest of an output row is zero.
+        delay, code1 and code2 are None when there are several pairs: they are per flow."""
+        import numpy as np
+        if pairs is None or code_of is None:  # what the library answers to a null pointer
+            raise FecError(FEC_ERR_ARG, "fec_mw_relay_streams_create_mixed")
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 6)
+        cof = np.ascontiguousarray(code_of, dtype=np.int32).reshape(-1)
+        h = ctypes.c_void_p()
+        check(lib().fec_mw_relay_streams_create_mixed(max_payload, pr.ctypes.data_as(ctypes.c_void_p), pr.shape[0],
+                                                      cof.ctypes.data_as(ctypes.c_void_p), cof.size, ctypes.byref(h)),
+              "fec_mw_relay_streams_create_mixed")
+        self = cls.__new__(cls)
+        self._h = h
+        self.L, self.nstreams = max_payload, cof.size
+        v = [ctypes.c_int() for _ in range(3)]
+        check(lib().fec_mw_relay_streams_codes(h, *[ctypes.byref(x) for x in v]), "fec_mw_relay_streams_codes")
+        nc, self.cw1_bytes, self.cw2_bytes = (x.value for x in v)
+        assert nc == pr.shape[0]
+        self.codes = [(tuple(int(x) for x in p[:3]), tuple(int(x) for x in p[3:])) for p in pr]
+        self.code_of = [self.geometry(s)["code"] for s in range(cof.size)]
+        if nc == 1:
+            self.delay = self.geometry(0)["delay"]
+            self.code1, self.code2 = self.codes[0]
+        else:
+            self.delay = self.code1 = self.code2 = None
+        return self
+
+    def geometry(self, stream_id: int) -> dict:
+        """Flow `stream_id`'s pair index and that pair's k1, n1, k2, n2, cw1_bytes, cw2_bytes and delay."""
+        v = [ctypes.c_int() for _ in range(8)]
+        check(lib().fec_mw_relay_streams_stream_geometry(self._h, stream_id, *[ctypes.byref(x) for x in v]),
+              "fec_mw_relay_streams_stream_geometry")
+        return dict(zip(("code", "k1", "n1", "k2", "n2", "cw1_bytes", "cw2_bytes", "delay"), (x.value for x in v)))
+
+    def set_code(self, stream_id: int, code: int) -> None:
+        """Flow `stream_id` becomes a fresh hop-1 decoder and a fresh hop-2 encoder of pair `code` (seq 0,
+        no erasure behind it); the old pair's last T1 messages are never forwarded."""
+        check(lib().fec_mw_relay_streams_set_code(self._h, stream_id, code), "fec_mw_relay_streams_set_code")
+        self.code_of[stream_id] = code
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -344,6 +394,20 @@ def mw_relay_streams_fit(max_payload: int, code1, code2):
     check(lib().fec_mw_relay_streams_fit(max_payload, *code1, *code2, ctypes.byref(tp), ctypes.byref(lds)),
           "fec_mw_relay_streams_fit")
     return tp.value, lds.value
+
+
+def mw_relay_streams_mixed_fit(max_payload: int, pairs):
+    """Host only: per pair of a mixed message-wise relay group (packets per chunk of a burst cut in
+    several, that chunk's LDS bytes) as int32 arrays [ncodes] (fec_mw_relay_streams_mixed_fit); FecError
+    if a pair is refused."""
+    import numpy as np
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 6)
+    nc = pr.shape[0]
+    res = [np.zeros(max(nc, 1), dtype=np.int32) for _ in range(2)]
+    check(lib().fec_mw_relay_streams_mixed_fit(max_payload, pr.ctypes.data_as(ctypes.c_void_p), nc,
+                                               *[r.ctypes.data_as(ctypes.c_void_p) for r in res]),
+          "fec_mw_relay_streams_mixed_fit")
+    return tuple(r[:nc] for r in res)
 
 
 class StateDependentRelay:

@@ -567,12 +567,60 @@ typedef struct fec_mw_relay_streams fec_mw_relay_streams;
 int fec_mw_relay_streams_create(int max_payload, int T1, int B1, int N1, int T2, int B2, int N2, int nstreams,
                                 fec_mw_relay_streams **out);
 int fec_mw_relay_streams_destroy(fec_mw_relay_streams *group);
-/* cw1_bytes = S1*n1, cw2_bytes = S2*n2, delay = T1 (any pointer may be NULL) */
+/* Mixed groups: every flow has its own pair of codes (T1,B1,N1) -> (T2,B2,N2), and one call serves
+ * flows of different pairs in one launch -- the relay node of many flows under the adaptive loop, each
+ * hop of each flow on the code its own loss calls for.  This replaces one fec_mw_relay_streams_create
+ * group and one call per pair.  pairs: ncodes x {T1,B1,N1,T2,B2,N2} (1 <= ncodes <= 64, equal pairs
+ * may repeat), code_of: nstreams indices into it.  FEC_ERR_ARG, nothing created: a pair
+ * fec_mw_relay_streams_create refuses at this max_payload (a tuple fec_streams_create refuses, or a
+ * smallest chunk T1+k1-1 + n2-1 over 32 packets or over a CU's LDS; fec_mw_relay_streams_mixed_fit), a
+ * code index outside [0, ncodes), ncodes out of range, a null pointer.  The result is an ordinary
+ * group: fec_mw_relay_streams_relay / _state / _destroy take it unchanged, with this row layout: each
+ * row array has one stride for the whole group (fec_mw_relay_streams_codes).  d_cw1 rows: cw1_stride >=
+ * the largest S1*n1 of the group's pairs; a flow's codeword is the first S1*n1 bytes of its own code,
+ * the rest of the row and rows of erased packets are never read.  d_cw2 rows: cw2_stride = the largest
+ * S2*n2; the flow's hop-2 codeword, then zeros up to the stride (a row of hop-1 seq < T1 is zero
+ * across the whole stride); nothing outside a row is written.  d_cw2_len, d_fate: as in a one-code
+ * group.  Per flow, the rows of all calls together equal the one-code contract of the flow's own pair
+ * (fec_streams_decode_burst over its hop-1 sequence, the first T1 rows dropped, then
+ * fec_streams_encode_burst with lengths clipped to [0, max_payload]) byte for byte, sizes and fates
+ * too, whatever the cutting into one-packet calls and bursts and whichever flows share a call.  No
+ * pointer or row needs any alignment.
+ * The table-driven kernel runs the one-code kernel's chunk body with the pair's geometry from a table
+ * in device memory; a call cuts a flow's burst into chunks of min(the call's longest burst, its pair's
+ * chunk size) packets, and a launch takes the LDS of the largest such chunk among the pairs present in
+ * that call.  Device state per flow: a codeword ring slot of 64 x max_c(S1_c n1_c) bytes and a window
+ * slot of max_c(max(n2_c - 1, 1) S2_c k2_c) bytes rounded up to 16; one codec per distinct hop code. */
+int fec_mw_relay_streams_create_mixed(int max_payload, const int32_t *pairs, int ncodes,
+                                      const int32_t *code_of, int nstreams, fec_mw_relay_streams **out);
+/* The number of pairs of a group (1 for fec_mw_relay_streams_create's, whose strides are its own
+ * sizes) and its row strides: the least cw1_stride and the output rows' (any pointer may be NULL). */
+int fec_mw_relay_streams_codes(const fec_mw_relay_streams *group, int *ncodes, int *cw1_bytes, int *cw2_stride);
+/* Flow `id`'s pair index and that pair's sizes: cw1_bytes = S1*n1, cw2_bytes = S2*n2, delay = T1 (any
+ * pointer may be NULL). */
+int fec_mw_relay_streams_stream_geometry(const fec_mw_relay_streams *group, int id, int *code, int *k1, int *n1,
+                                         int *k2, int *n2, int *cw1_bytes, int *cw2_bytes, int *delay);
+/* Makes flow `id` a fresh hop-1 decoder and a fresh hop-2 encoder of pair `code`: seq 0 and a new
+ * symbolic decoder on that pair's decode rules.  Host work only (calls already queued carry their own
+ * seqs and pairs; the slot's device bytes are not cleared, and the kernels never read a flow's device
+ * state from before seq 0).  The old pair's last T1 messages are never forwarded: a caller that wants
+ * them keeps the old id alive beside a second id.  On a group made by fec_mw_relay_streams_create only
+ * code 0 is accepted, and resets the flow.  FEC_ERR_ARG (group unchanged): id or code out of range. */
+int fec_mw_relay_streams_set_code(fec_mw_relay_streams *group, int id, int code);
+/* Host only, no device call: per pair the packets per chunk of a burst cut in several and that
+ * chunk's LDS bytes (ncodes entries each): entry c is fec_mw_relay_streams_fit of pair c, through the
+ * routine create uses.  FEC_ERR_ARG if any pair is refused, ncodes is outside [1, 64] or a pointer is
+ * null. */
+int fec_mw_relay_streams_mixed_fit(int max_payload, const int32_t *pairs, int ncodes, int32_t *chunk,
+                                   int32_t *lds);
+/* cw1_bytes = S1*n1, cw2_bytes = S2*n2, delay = T1 (any pointer may be NULL).  A group of one pair;
+ * FEC_ERR_ARG for a group of several (fec_mw_relay_streams_stream_geometry answers per flow). */
 int fec_mw_relay_streams_geometry(const fec_mw_relay_streams *group, int *cw1_bytes, int *cw2_bytes, int *delay);
 int fec_mw_relay_streams_relay(fec_mw_relay_streams *group, const int32_t *ids, const int32_t *counts, int M,
                                const uint8_t *erasure, const uint8_t *d_cw1, int64_t cw1_stride, uint8_t *d_cw2,
                                int32_t *d_cw2_len, uint8_t *d_fate, void *hip_stream);
-/* hop-1 packets flow id has been fed so far, and messages forwarded (= max(received - T1, 0)) */
+/* hop-1 packets flow id has been fed so far, and messages forwarded (= max(received - T1, 0), T1 the
+ * flow's own) */
 int fec_mw_relay_streams_state(const fec_mw_relay_streams *group, int id, int64_t *received, int64_t *forwarded);
 /* Host only, no device call: the packets per chunk of a burst cut in several and that chunk's LDS
  * bytes, through the routine create uses.  FEC_ERR_ARG where create would refuse the pair. */
